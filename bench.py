@@ -8,10 +8,22 @@ rtol 1e-8, warm start) -> correction + min/max (K5), on the 4096^2 cavity (fp64,
 dt = 1/(8n)), inputs resident in HBM.  N > 1: x-slabs, one rank per GPU, RCCL halos
 (strong scaling: the global grid is fixed).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--n 4096] [--re 1000] [--no-cpu]
-                  [--transport rccl|host]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--n 4096] [--re 1000] [--full [--no-cpu]
+                  [--no-jacobi]] [--dump-outputs DIR] [--transport rccl|host]
   (N > 1 under torch.distributed.run; RANK / WORLD_SIZE / LOCAL_RANK from the env; without a
   launcher, --gpus N starts its own N ranks and relays rank 0's JSON line)
+
+A plain run does what the headline figure needs: set-up, W warm-up steps, the K timed steps
+(`ms_per_step` = their wall time / K), the JSON line.  --full adds the legs that take runs of
+their own after the timed region: the Jacobi-sweep roofline kernels (fp64, fp32 fields) and
+the CPU baseline with its parity check against the oracle (--no-jacobi / --no-cpu drop one).
+
+--dump-outputs DIR: after the timed steps, what the last timed step left a caller of the
+timed path -- the velocity and pressure-correction planes u, v, phi (ns_get_array) and the
+monitor (umin, umax, vmin, vmax) -- as DIR/<name>.npy, float64 (N > 1: <name>_rank<r>.npy,
+each rank's slab).  Planes that together exceed DUMP_BUDGET_BYTES are written as the same
+fixed sample of cells (dump_sample: seeded, a function of the plane's shape only), so two
+builds run with the same arguments can be compared output for output.
 
 --transport host (or NSBENCH_TRANSPORT=host): the N > 1 branch as a rehearsal on ONE GPU -- every
 rank on device 0, the ghost rows / gathers / reductions through the host (gloo) instead of RCCL
@@ -115,9 +127,15 @@ def parse(argv=None):
                     help="--case stretched / xstretched: the face-spacing ratio (Nx / Ny {0 1 n ratio})")
     ap.add_argument("--re", type=float, default=1000.0)
     ap.add_argument("--rtol", type=float, default=1e-8)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs beside the headline figure: the Jacobi-sweep "
+                         "roofline kernels and the CPU baseline with its parity check against the oracle")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
     ap.add_argument("--no-jacobi", action="store_true",
-                    help="skip the Jacobi-sweep roofline leg (kernel traces of the step alone)")
+                    help="--full: skip the Jacobi-sweep roofline leg (kernel traces of the step alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write u, v, phi and the monitor of the last timed step as DIR/<name>.npy (float64; a "
+                         "fixed seeded sample of cells when the planes exceed DUMP_BUDGET_BYTES)")
     ap.add_argument("--sync-monitor", action="store_true",
                     help="ns_step (host sync at every step's end) instead of ns_step_async")
     ap.add_argument("--transport", choices=("rccl", "host"), default=os.environ.get("NSBENCH_TRANSPORT", "rccl"),
@@ -177,6 +195,38 @@ def helm_passes(n, min_rows):
         r -= w
         p += 1
     return p
+
+
+DUMP_BUDGET_BYTES = 48 << 20   # --dump-outputs: all the files of one run together stay below 64 MB
+DUMP_SEED = 0x5EED
+
+
+def dump_sample(shape, count):
+    """The cells a plane too large for the budget is sampled at: `count` flat indices into a plane
+    of `shape`, ascending, drawn once from a fixed seed -- the same for every run, build and field."""
+    import numpy as np
+    size = int(np.prod(shape))
+    return np.sort(np.random.default_rng([DUMP_SEED, *shape]).integers(0, size, count))
+
+
+def dump_outputs(path, solver, monitor, rank, world):
+    """--dump-outputs: this rank's u, v, phi planes as the last timed step left them (whole, or at
+    dump_sample's cells) and that step's monitor, float64 .npy files under `path`."""
+    import numpy as np
+    import navierstokessolver_amd as nsa
+    os.makedirs(path, exist_ok=True)
+    tag = "" if world == 1 else f"_rank{rank}"
+    planes = (("u", nsa.NS_ARR_U), ("v", nsa.NS_ARR_V), ("phi", nsa.NS_ARR_PHI))
+    cells = solver.shape[0] * solver.shape[1]
+    per_plane = DUMP_BUDGET_BYTES // (8 * len(planes) * world)
+    idx = dump_sample(solver.shape, per_plane) if cells > per_plane else None
+    for name, which in planes:
+        a = solver.get(which)
+        a = a.ravel()[idx] if idx is not None else a
+        np.save(os.path.join(path, f"{name}{tag}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+    if rank == 0:
+        np.save(os.path.join(path, "monitor.npy"),
+                np.array([monitor[k] for k in ("umin", "umax", "vmin", "vmax")], dtype=np.float64))
 
 
 def cpu_baseline(n, re, dt, omega_v, omega_mg, state, gpu_next=None):
@@ -425,6 +475,8 @@ def run(args, rank, world, local, wd):
         per_rank = [None] * world
         dist.all_gather_object(per_rank, mine)
         elapsed = max(p["ms_per_step"] for p in per_rank) * args.steps / 1e3
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, solver, last_monitor, rank, world)
 
     K = args.steps
     timed_steps = K if args.time_every == 1 else (sum(1 for k in range(K) if k % args.time_every == min(1, K - 1))
@@ -520,9 +572,9 @@ def run(args, rank, world, local, wd):
                         sum(s["n_rhs_kernels"] for s in stats if s["k5_deferred"]))
 
     # the north star's roofline kernel: one Jacobi sweep of this rank's slab (random phi, b;
-    # 10 warm-up + 50 timed launches, HIP events), single rank only
+    # 10 warm-up + 50 timed launches, HIP events), single rank only, --full
     jacobi = jacobi32 = None
-    if world == 1 and args.case == "cavity" and not args.no_jacobi:
+    if args.full and world == 1 and args.case == "cavity" and not args.no_jacobi:
         js = nsa.GpuSolver(nsa.cavity(n), dt, re, poisson=nsa.NS_POISSON_JACOBI, omega=1.0, device=device)
         js.fill_random(0x5EED)
         t = js.time_poisson(10, 50)
@@ -672,7 +724,7 @@ def run(args, rank, world, local, wd):
                                 "groups"}
     else:
         line.pop("ranks")
-    if world == 1 and not args.no_cpu and args.case == "cavity" and n & (n - 1) == 0:
+    if args.full and world == 1 and not args.no_cpu and args.case == "cavity" and n & (n - 1) == 0:
         try:
             state = {k: solver.get(a).ravel() for k, a in (("u", nsa.NS_ARR_U), ("v", nsa.NS_ARR_V),
                                                            ("phi", nsa.NS_ARR_PHI), ("cu", nsa.NS_ARR_CU),

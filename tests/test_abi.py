@@ -29,7 +29,7 @@ def test_lib_is_gfx950_code_object():
     assert "gfx950" in out
 
 
-def _c_sizes():
+def _c_sizes(tmp_path):
     src = r'''
 #include <stdio.h>
 #include <stddef.h>
@@ -40,14 +40,14 @@ int main(void){
         offsetof(ns_grid_desc, cell_id), offsetof(ns_grid_desc, face_edge));
  return 0;}
 '''
-    exe = "/tmp/ns_abi_sizes"
+    exe = str(tmp_path / "ns_abi_sizes")
     subprocess.run(["gcc", "-x", "c", "-I", os.path.join(ROOT, "include"), "-o", exe, "-"], input=src, text=True,
                    check=True)
     return [int(x) for x in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
 
 
-def test_ctypes_struct_layout_matches_c():
-    c = _c_sizes()
+def test_ctypes_struct_layout_matches_c(tmp_path):
+    c = _c_sizes(tmp_path)
     py = [ctypes.sizeof(L.NsEdge), ctypes.sizeof(L.NsGridDesc), ctypes.sizeof(L.NsParams),
           ctypes.sizeof(L.NsStats), L.NsParams.nccl_id.offset, L.NsStats.t_poisson_kernel_ms.offset,
           L.NsGridDesc.cell_id.offset, L.NsGridDesc.face_edge.offset]

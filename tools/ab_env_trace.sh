@@ -7,7 +7,7 @@ out=$1; var=$2; shift 2
 export TMPDIR=/tmp
 mkdir -p $out
 for v in "$@"; do
-  env $var=$v timeout -k 10 200 python3 bench.py --steps 20 --warmup 5 --no-cpu > $out/bench_$v.json 2> $out/bench_$v.err
+  env $var=$v timeout -k 10 200 python3 bench.py --full --steps 20 --warmup 5 --no-cpu > $out/bench_$v.json 2> $out/bench_$v.err
   python3 -c "
 import json; d=json.loads(open('$out/bench_$v.json').read().strip().splitlines()[-1]); print('$var=$v', round(d['value']), round(d['ms_per_step'], 4))"
 done

@@ -8,7 +8,7 @@ for rep in 1 2; do
   k=0
   for lib in "$@"; do
     k=$((k + 1))
-    NSGPU_LIB=$lib timeout -k 10 200 python bench.py --steps ${STEPS:-20} --warmup ${WARMUP:-10} --no-cpu \
+    NSGPU_LIB=$lib timeout -k 10 200 python bench.py --full --steps ${STEPS:-20} --warmup ${WARMUP:-10} --no-cpu \
       > gpurun_out/ablib_${k}_$rep.log 2>&1
     python3 -c "
 import json; d=json.loads(open('gpurun_out/ablib_${k}_$rep.log').read().strip().splitlines()[-1])

@@ -24,23 +24,23 @@ suite)
   rc=$?; grep -E "passed|failed" $out/pytest_gpu.log | tail -2; grep -E "^FAILED" $out/pytest_gpu.log | head
   exit $rc ;;
 bench)
-  timeout -k 10 400 python -u bench.py > $out/bench_default.log 2>&1 || exit $?
+  timeout -k 10 400 python -u bench.py --full > $out/bench_default.log 2>&1 || exit $?
   line default $out/bench_default.log
-  timeout -k 10 400 python -u bench.py --warmup 5 --steps 20 > $out/bench_driver_form.log 2>&1 || exit $?
+  timeout -k 10 400 python -u bench.py --full --warmup 5 --steps 20 > $out/bench_driver_form.log 2>&1 || exit $?
   line driver_form $out/bench_driver_form.log
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o run -- \
-    python3 bench.py --warmup 5 --steps 20 --no-cpu > $out/trace.log 2>&1 || exit $?
+    python3 bench.py --full --warmup 5 --steps 20 --no-cpu > $out/trace.log 2>&1 || exit $?
   python3 tools/trace_summary.py $(find $out/trace -name "*kernel_trace.csv" | head -1) 25 > $out/per_step_summary.txt
   head -16 $out/per_step_summary.txt ;;
 pmc)
   bash tools/profile_round.sh $out > $out/profile_round.log 2>&1 || exit $?
   tail -3 $out/profile_round.log ;;
 sizes)
-  timeout -k 10 200 python -u bench.py --n 2048 --warmup 5 --steps 20 --no-cpu > $out/n2048.log 2>&1 || exit $?
+  timeout -k 10 200 python -u bench.py --full --n 2048 --warmup 5 --steps 20 --no-cpu > $out/n2048.log 2>&1 || exit $?
   line n2048 $out/n2048.log
-  timeout -k 10 300 python -u bench.py --n 8192 --warmup 5 --steps 10 --no-cpu > $out/n8192.log 2>&1 || exit $?
+  timeout -k 10 300 python -u bench.py --full --n 8192 --warmup 5 --steps 10 --no-cpu > $out/n8192.log 2>&1 || exit $?
   line n8192 $out/n8192.log
-  timeout -k 10 400 python -u bench.py --n 16384 --warmup 3 --steps 4 --no-cpu > $out/n16384.log 2>&1 || exit $?
+  timeout -k 10 400 python -u bench.py --full --n 16384 --warmup 3 --steps 4 --no-cpu > $out/n16384.log 2>&1 || exit $?
   line n16384 $out/n16384.log ;;
 projection)
   timeout -k 10 600 python3 -u tools/slab_projection.py --n 4096 --ranks 1,2,4,8 > $out/projection_4096.log 2>&1 || exit $?
@@ -52,7 +52,7 @@ projection)
   tail -1 $out/projection_weak.log ;;
 devflow)
   for w in 5 10 2000; do
-    timeout -k 10 200 python -u bench.py --no-cpu --warmup $w --steps 40 --time-every 0 > $out/bench_w$w.log 2>&1 || exit $?
+    timeout -k 10 200 python -u bench.py --full --no-cpu --warmup $w --steps 40 --time-every 0 > $out/bench_w$w.log 2>&1 || exit $?
     line "warmup_$w" $out/bench_w$w.log
   done ;;
 jacobi)
@@ -70,13 +70,13 @@ fallbacks)
     head -14 $out/${nm}_summary.txt
   }
   for c in stretched xstretched; do
-    timeout -k 10 300 python -u bench.py --case $c --warmup 5 --steps 20 > $out/$c.log 2>&1 || exit $?
+    timeout -k 10 300 python -u bench.py --full --case $c --warmup 5 --steps 20 > $out/$c.log 2>&1 || exit $?
     line $c $out/$c.log
-    trace $c 25 bench.py --case $c --warmup 5 --steps 20 --no-cpu || exit $?
+    trace $c 25 bench.py --full --case $c --warmup 5 --steps 20 --no-cpu || exit $?
   done
-  timeout -k 10 300 python -u bench.py --n 4000 --warmup 5 --steps 20 > $out/n4000.log 2>&1 || exit $?
+  timeout -k 10 300 python -u bench.py --full --n 4000 --warmup 5 --steps 20 > $out/n4000.log 2>&1 || exit $?
   line n4000 $out/n4000.log
-  trace n4000 25 bench.py --n 4000 --warmup 5 --steps 20 --no-cpu || exit $?
+  trace n4000 25 bench.py --full --n 4000 --warmup 5 --steps 20 --no-cpu || exit $?
   timeout -k 10 400 python -u bench.py --case channel --gpus 2 --transport host --warmup 3 --steps 10 \
     > $out/channel_host2.log 2>&1 || exit $?
   line channel_host2 $out/channel_host2.log

@@ -65,7 +65,7 @@ res = {"n": n, "kernels": {},
        # the stamp bench.py copies into each roofline.traffic: which run and which library measured it
        "source": {"fetch_dir": fetch_dir, "write_dir": write_dir,
                   "command": os.environ.get("PMC_COMMAND", "rocprofv3 --pmc FETCH_SIZE (then WRITE_SIZE) -- "
-                                            "python3 bench.py --steps 3 --warmup 1 --no-cpu"),
+                                            "python3 bench.py --full --steps 3 --warmup 1 --no-cpu"),
                   "libnsgpu_sha16": _sha16(os.path.join(ROOT, "navierstokessolver_amd", "libnsgpu.so"))}}
 for spec in sys.argv[5:]:
     key, rx, bpc = spec.split("=")

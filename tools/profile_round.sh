@@ -9,11 +9,11 @@ set -e
 out=${1:-gpurun_out/prof}
 export TMPDIR=/tmp
 mkdir -p $out
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o run -- python3 bench.py --steps 10 --warmup 3 --no-cpu > $out/trace.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o run -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu > $out/trace.log 2>&1
 python3 tools/trace_summary.py $(find $out/trace -name "*kernel_trace.csv" | head -1) 13 > $out/per_step_summary.txt
-timeout -s KILL 200 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/fetch -o run -- python3 bench.py --steps 3 --warmup 1 --no-cpu > $out/fetch.log 2>&1
-timeout -s KILL 200 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/write -o run -- python3 bench.py --steps 3 --warmup 1 --no-cpu > $out/write.log 2>&1
-timeout -s KILL 200 rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES --output-format csv -d $out/valu -o run -- python3 bench.py --steps 3 --warmup 1 --no-cpu > $out/valu.log 2>&1
+timeout -s KILL 200 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/fetch -o run -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu > $out/fetch.log 2>&1
+timeout -s KILL 200 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/write -o run -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu > $out/write.log 2>&1
+timeout -s KILL 200 rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES --output-format csv -d $out/valu -o run -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu > $out/valu.log 2>&1
 python3 tools/pmc_summarize.py 4096 $out/fetch $out/write $out/pmc_traffic.json \
   'restrict=k_sweep2<0, false, 1=26' 'prolong=k_sweep2<0, (true|false), 2=26' 'cycle=k_sweep4=28' \
   'jacobi_sweep=k_jacobi_s<double=24' 'jacobi_sweep_fp32=k_jacobi_s<float=12' \
