@@ -1659,7 +1659,7 @@ __global__ void __launch_bounds__(64 * FPS_G) k_fps_t2b(FpsArgs a, double* __res
     }
 }
 
-bool fps_div_real(int logn, int outE);
+bool fps_div_real(const Knobs& k, int logn, int outE);
 template <int LOGN>
 void idct_row(const double* in, double* out, int nrows, int ld, const void* tw, const void* wk, hipStream_t st) {
     const size_t lr = sizeof(cplx) * (size_t)RFft<LOGN>::M;
@@ -1673,16 +1673,15 @@ void idct_row(const double* in, double* out, int nrows, int ld, const void* tw, 
                            (const cplx*)tw, (const cplx*)wk);
 }
 template <int LOGN>
-void dct_pair(bool inverse, const double* in, const double* shift, double* out, int nrows, int ld, const void* tw,
+void dct_pair(const Knobs& k, bool inverse, const double* in, const double* shift, double* out, int nrows, int ld, const void* tw,
               const void* wk, hipStream_t st, int oe_pair, const int32_t* fcm = nullptr) {
     constexpr int T = Fft<LOGN>::T;
     const size_t lds = sizeof(cplx) * (size_t)FftLds<LOGN>::n;
     // (r6) one workgroup per row pair: 106.5 / 64.6 us at 4096^2 against 110.7 / 65.6 with r4-r5's one persistent
     // round of two per CU (profiles/r06/ab/fpsg_summary.txt); NSGPU_FPS_GRID=n: at most n workgroups (A/B)
-    static const int fg = getenv("NSGPU_FPS_GRID") ? std::atoi(getenv("NSGPU_FPS_GRID")) : 0;
-    const dim3 grid(std::min((nrows + 1) / 2, fg > 0 ? fg : 1 << 30));
+    const dim3 grid(std::min((nrows + 1) / 2, k.fps_grid > 0 ? k.fps_grid : 1 << 30));
     if constexpr (LOGN >= 10 && LOGN <= 13) {
-        if (inverse && !fcm && fps_div_real(LOGN, 0)) {   // (r6: one row per workgroup, k_fps_idct_r)
+        if (inverse && !fcm && fps_div_real(k, LOGN, 0)) {   // (r6: one row per workgroup, k_fps_idct_r)
             idct_row<LOGN>(in, out, nrows, ld, tw, wk, st);
             return;
         }
@@ -1709,9 +1708,8 @@ void dct_pair(bool inverse, const double* in, const double* shift, double* out, 
 }
 
 // (r6) the one-row-per-workgroup transform (k_fps_dct_div_r): 2 cnt workgroups; NSGPU_FPS_REAL=0: the pairs (A/B)
-bool fps_div_real(int logn, int outE) {
-    const char* e = getenv("NSGPU_FPS_REAL");   // (read per launch: the parity test switches it)
-    return (!e || std::atoi(e) != 0) && !outE && logn >= 10 && logn <= 14;
+bool fps_div_real(const Knobs& k, int logn, int outE) {
+    return k.fps_real && !outE && logn >= 10 && logn <= 14;
 }
 template <int LOGN>
 int div_row(const FpsDivArgs& a0, hipStream_t st) {
@@ -1729,12 +1727,11 @@ int div_row(const FpsDivArgs& a0, hipStream_t st) {
 }
 
 template <int LOGN>
-int div_pair(const FpsDivArgs& a0, hipStream_t st) {
+int div_pair(const Knobs& k, const FpsDivArgs& a0, hipStream_t st) {
     constexpr int T = Fft<LOGN>::T;
     const size_t lds = sizeof(cplx) * (size_t)FftLds<LOGN>::n;
     lds_attr_once((const void*)k_fps_dct_div<LOGN>, (int)lds);
-    static const int fg = getenv("NSGPU_FPS_GRID") ? std::atoi(getenv("NSGPU_FPS_GRID")) : 0;   // (as dct_pair)
-    const dim3 grid(std::min(a0.cnt, fg > 0 ? fg : 1 << 30));
+    const dim3 grid(std::min(a0.cnt, k.fps_grid > 0 ? k.fps_grid : 1 << 30));   // (as dct_pair)
     hipEvent_t a, b;
     if (take_launch_timing(a, b)) hipExtLaunchKernelGGL(k_fps_dct_div<LOGN>, grid, dim3(T), lds, st, a, b, 0, a0);
     else hipLaunchKernelGGL(k_fps_dct_div<LOGN>, grid, dim3(T), lds, st, a0);
@@ -2107,22 +2104,22 @@ bool fps_idct_mask_ok(int ny) {
     const int l = fps_log2(ny);
     return FPS_REGIO && FPS_LR == 4 && FPS_ISTAGE && l >= 10 && l <= 13;
 }
-int launch_fps_idct_masked(const double* in, double* out, int nrows, int ny, int ld, const double* tw, const double* wk,
+int launch_fps_idct_masked(const Knobs& k, const double* in, double* out, int nrows, int ny, int ld, const double* tw, const double* wk,
                            hipStream_t st, const int32_t* fcm) {
     if (!fps_idct_mask_ok(ny)) return -1;
     switch (fps_log2(ny)) {
-    case 10: dct_pair<10>(true, in, nullptr, out, nrows, ld, tw, wk, st, -1, fcm); break;
-    case 11: dct_pair<11>(true, in, nullptr, out, nrows, ld, tw, wk, st, -1, fcm); break;
-    case 12: dct_pair<12>(true, in, nullptr, out, nrows, ld, tw, wk, st, -1, fcm); break;
-    case 13: dct_pair<13>(true, in, nullptr, out, nrows, ld, tw, wk, st, -1, fcm); break;
+    case 10: dct_pair<10>(k, true, in, nullptr, out, nrows, ld, tw, wk, st, -1, fcm); break;
+    case 11: dct_pair<11>(k, true, in, nullptr, out, nrows, ld, tw, wk, st, -1, fcm); break;
+    case 12: dct_pair<12>(k, true, in, nullptr, out, nrows, ld, tw, wk, st, -1, fcm); break;
+    case 13: dct_pair<13>(k, true, in, nullptr, out, nrows, ld, tw, wk, st, -1, fcm); break;
     default: return -1;
     }
     return 0;
 }
 
-int launch_fps_dct(bool inverse, const double* in, const double* shift, double* out, int nrows, int ny, int ld,
+int launch_fps_dct(const Knobs& k, bool inverse, const double* in, const double* shift, double* out, int nrows, int ny, int ld,
                    const double* tw, const double* wk, hipStream_t st, int oe_pair, const double* tw8) {
-    if (ny == N14 && inverse && fps_div_real(14, 0)) {   // (r6: one row per workgroup, 1024 threads)
+    if (ny == N14 && inverse && fps_div_real(k, 14, 0)) {   // (r6: one row per workgroup, 1024 threads)
         idct_row<14>(in, out, nrows, ld, tw, wk, st);
         return 0;
     }
@@ -2158,22 +2155,22 @@ int launch_fps_dct(bool inverse, const double* in, const double* shift, double* 
         return 0;
     }
     switch (fps_log2(ny)) {
-    case 4: dct_pair<4>(inverse, in, shift, out, nrows, ld, tw, wk, st, oe_pair); break;
-    case 5: dct_pair<5>(inverse, in, shift, out, nrows, ld, tw, wk, st, oe_pair); break;
-    case 6: dct_pair<6>(inverse, in, shift, out, nrows, ld, tw, wk, st, oe_pair); break;
-    case 7: dct_pair<7>(inverse, in, shift, out, nrows, ld, tw, wk, st, oe_pair); break;
-    case 8: dct_pair<8>(inverse, in, shift, out, nrows, ld, tw, wk, st, oe_pair); break;
-    case 9: dct_pair<9>(inverse, in, shift, out, nrows, ld, tw, wk, st, oe_pair); break;
-    case 10: dct_pair<10>(inverse, in, shift, out, nrows, ld, tw, wk, st, oe_pair); break;
-    case 11: dct_pair<11>(inverse, in, shift, out, nrows, ld, tw, wk, st, oe_pair); break;
-    case 12: dct_pair<12>(inverse, in, shift, out, nrows, ld, tw, wk, st, oe_pair); break;
-    case 13: dct_pair<13>(inverse, in, shift, out, nrows, ld, tw, wk, st, oe_pair); break;
+    case 4: dct_pair<4>(k, inverse, in, shift, out, nrows, ld, tw, wk, st, oe_pair); break;
+    case 5: dct_pair<5>(k, inverse, in, shift, out, nrows, ld, tw, wk, st, oe_pair); break;
+    case 6: dct_pair<6>(k, inverse, in, shift, out, nrows, ld, tw, wk, st, oe_pair); break;
+    case 7: dct_pair<7>(k, inverse, in, shift, out, nrows, ld, tw, wk, st, oe_pair); break;
+    case 8: dct_pair<8>(k, inverse, in, shift, out, nrows, ld, tw, wk, st, oe_pair); break;
+    case 9: dct_pair<9>(k, inverse, in, shift, out, nrows, ld, tw, wk, st, oe_pair); break;
+    case 10: dct_pair<10>(k, inverse, in, shift, out, nrows, ld, tw, wk, st, oe_pair); break;
+    case 11: dct_pair<11>(k, inverse, in, shift, out, nrows, ld, tw, wk, st, oe_pair); break;
+    case 12: dct_pair<12>(k, inverse, in, shift, out, nrows, ld, tw, wk, st, oe_pair); break;
+    case 13: dct_pair<13>(k, inverse, in, shift, out, nrows, ld, tw, wk, st, oe_pair); break;
     default: return -1;
     }
     return 0;
 }
 
-int launch_fps_div(const Geo& g, const Coef& c, double dt, const double* u, const double* v, double* b, double* out,
+int launch_fps_div(const Knobs& k, const Geo& g, const Coef& c, double dt, const double* u, const double* v, double* b, double* out,
                    double* part, int phase, const double* tw, const double* wk, hipStream_t st, int outE) {
     const int np = (g.nxl + 1) / 2;
     FpsDivArgs a{g, c, 1.0 / dt, u, v, b, out, part, g.nxl, g.ld, 0, np, 1, (const cplx*)tw, (const cplx*)wk, outE};
@@ -2185,7 +2182,7 @@ int launch_fps_div(const Geo& g, const Coef& c, double dt, const double* u, cons
         a.pstep = std::max(np - 1, 1);
     }
     const int lg = g.ny == (1 << 14) ? 14 : fps_log2(g.ny);
-    if (fps_div_real(lg, outE)) {   // (per-row sums: 2 np partials)
+    if (fps_div_real(k, lg, outE)) {   // (per-row sums: 2 np partials)
         if (a.cnt <= 0) return 2 * np;
         int n = -1;
         switch (lg) {
@@ -2201,16 +2198,16 @@ int launch_fps_div(const Geo& g, const Coef& c, double dt, const double* u, cons
     if (a.cnt <= 0) return np;
     int n = -1;
     switch (lg) {
-    case 4: n = div_pair<4>(a, st); break;
-    case 5: n = div_pair<5>(a, st); break;
-    case 6: n = div_pair<6>(a, st); break;
-    case 7: n = div_pair<7>(a, st); break;
-    case 8: n = div_pair<8>(a, st); break;
-    case 9: n = div_pair<9>(a, st); break;
-    case 10: n = div_pair<10>(a, st); break;
-    case 11: n = div_pair<11>(a, st); break;
-    case 12: n = div_pair<12>(a, st); break;
-    case 13: n = div_pair<13>(a, st); break;
+    case 4: n = div_pair<4>(k, a, st); break;
+    case 5: n = div_pair<5>(k, a, st); break;
+    case 6: n = div_pair<6>(k, a, st); break;
+    case 7: n = div_pair<7>(k, a, st); break;
+    case 8: n = div_pair<8>(k, a, st); break;
+    case 9: n = div_pair<9>(k, a, st); break;
+    case 10: n = div_pair<10>(k, a, st); break;
+    case 11: n = div_pair<11>(k, a, st); break;
+    case 12: n = div_pair<12>(k, a, st); break;
+    case 13: n = div_pair<13>(k, a, st); break;
     default: return -1;
     }
     return n < 0 ? -1 : np;
@@ -2218,7 +2215,7 @@ int launch_fps_div(const Geo& g, const Coef& c, double dt, const double* u, cons
 
 // whether the step's divergence can go into the forward transform (launch_fps_div): the row pairs for ny = 2^p <= 8192,
 // the one-row transforms (r6) up to 16384
-bool fps_fuse_ok(int ny, int outE) { return ny == (1 << 14) ? fps_div_real(14, outE) : fps_log2(ny) >= 0; }
+bool fps_fuse_ok(const Knobs& k, int ny, int outE) { return ny == (1 << 14) ? fps_div_real(k, 14, outE) : fps_log2(ny) >= 0; }
 
 void launch_fps_t1(const FpsArgs& a, const double* f, hipStream_t st) {
     hipLaunchKernelGGL(k_fps_t1, dim3((a.ny + 127) / 128, a.ngrp), dim3(64, FPS_G), 0, st, a, f);

@@ -5,6 +5,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "ns_knobs.h"
+
 namespace nsg {
 
 constexpr int HALO = 7;  // ghost rows per side: K1's MUSCL stencil (2), the 2-sweep pass's cone (4),
@@ -87,25 +89,25 @@ struct Partials {
 // (r6) uo / vo / mm: the previous step's CorrectVelocities folded in (ns_solver's deferred K5, ns_step_async): u, v
 // are u*, v*, phi is phi^n; the corrected u, v of every cell go to uo, vo and their min / max partials (4 per
 // block, the same count as the return value) to mm.  Streaming kernel only (-1 otherwise)
-int launch_rhs(const Geo& g, const Coef& c, double dt, double re, const double* u, const double* v,
+int launch_rhs(const Knobs& kn, const Geo& g, const Coef& c, double dt, double re, const double* u, const double* v,
                const double* phi, double* cu, double* cv, double* ru, double* rv, double* part, hipStream_t st,
                int depth = 2, double* uo = nullptr, double* vo = nullptr, double* mm = nullptr);
 // K2: fused red-black SOR sweep of (I - a L_V) on u and v, (u,v) -> (uo,vo);
 //     residual^2 partials of the input if part != null: u at part[0..n), v at part[n..2n), n returned
-int launch_helm_sweep(const Geo& g, const Coef& c, double alpha, double omega, const double* u, const double* v,
+int launch_helm_sweep(const Knobs& kn, const Geo& g, const Coef& c, double alpha, double omega, const double* u, const double* v,
                       double* uo, double* vo, const double* ru, const double* rv, double* part, hipStream_t st,
                       int which = 3);
 // K3: divergence / dt  + partial sums (sum, sum^2)
-int launch_div(const Geo& g, const Coef& c, double dt, const double* u, const double* v, double* rp,
+int launch_div(const Knobs& kn, const Geo& g, const Coef& c, double dt, const double* u, const double* v, double* rp,
                double* part, hipStream_t st);
 // K4: fused red-black SOR Poisson sweep phi -> out; residual^2 partials of the input iterate
-int launch_pois_rbsor(const Geo& g, const Coef& c, double omega, const double* phi, double* out,
+int launch_pois_rbsor(const Knobs& kn, const Geo& g, const Coef& c, double omega, const double* phi, double* out,
                       const double* rp, const double* shift, double* part, hipStream_t st);
 // K4 Jacobi: out = in + w (b - shift - L in)/diag
-int launch_pois_jacobi(const Geo& g, const Coef& c, double omega, const double* in, double* out,
+int launch_pois_jacobi(const Knobs& kn, const Geo& g, const Coef& c, double omega, const double* in, double* out,
                        const double* rp, const double* shift, double* part, hipStream_t st);
 // K4 Jacobi on fp32 fields (rows of g.ld floats), fp64 arithmetic and residual partials
-int launch_pois_jacobi32(const Geo& g, const Coef& c, double omega, const float* in, float* out, const float* rp,
+int launch_pois_jacobi32(const Knobs& kn, const Geo& g, const Coef& c, double omega, const float* in, float* out, const float* rp,
                          const double* shift, double* part, hipStream_t st);
 // the slab's own rows fp64 -> fp32 and back
 void launch_to_f32(const Geo& g, const double* src, float* dst, hipStream_t st);
@@ -113,7 +115,7 @@ void launch_to_f64(const Geo& g, const float* src, double* dst, hipStream_t st);
 // two red-black sweeps in one HBM pass (temporal blocking): same results as two calls above;
 // residual partials (if part) are of the OUTPUT iterate, and then 5 ghost rows are read
 // (4 without)
-int launch_pois_rbsor2(const Geo& g, const Coef& c, double omega, const double* phi, double* out,
+int launch_pois_rbsor2(const Knobs& kn, const Geo& g, const Coef& c, double omega, const double* phi, double* out,
                        const double* rp, const double* shift, double* part, hipStream_t st);
 // K2: three RB-SOR sweeps per pass (k_sweep3; no residual partials); which as above
 // one launch of the Helmholtz wall-band relaxation (k_helm_band): 3 RB-SOR sweeps of u and v
@@ -124,10 +126,10 @@ int launch_helm_band(const Geo& g, const Coef& c, double alpha, double omega, co
                      const double* qu, const double* qv, double* ou, double* ov, const double* ru, const double* rv,
                      int bw, int copy, hipStream_t st);
 // part != null: the pass also sums its output's residual (one field, one rank; < 0 otherwise)
-int launch_helm_sweep3(const Geo& g, const Coef& c, double alpha, double omega, const double* u, const double* v,
+int launch_helm_sweep3(const Knobs& kn, const Geo& g, const Coef& c, double alpha, double omega, const double* u, const double* v,
                        double* uo, double* vo, const double* ru, const double* rv, hipStream_t st, int which,
                        double* part = nullptr);
-int launch_helm_sweep2(const Geo& g, const Coef& c, double alpha, double omega, const double* u, const double* v,
+int launch_helm_sweep2(const Knobs& kn, const Geo& g, const Coef& c, double alpha, double omega, const double* u, const double* v,
                        double* uo, double* vo, const double* ru, const double* rv, double* part, hipStream_t st,
                        int which = 3);
 // ns (3 or 4) Helmholtz sweeps of ONE component in one pass (q -> qo), a single slab only
@@ -139,7 +141,7 @@ int launch_pois_rbsor_tiled(const Geo& g, const Coef& c, double omega, const dou
                             const double* rp, const double* shift, double* part, hipStream_t st);
 int launch_pois_jacobi_tiled(const Geo& g, const Coef& c, double omega, const double* in, double* out,
                              const double* rp, const double* shift, double* part, hipStream_t st);
-// rows per streaming strip (tuning knob)
+// rows per streaming strip (Knobs::strip_rows; 0 = adaptive): process-wide, set by ns_create
 void set_strip_rows(int L);
 // CUs the following launches' streams may use (0 = all): sizes "one resident round" of strips
 void set_compute_cus(int n);
@@ -159,13 +161,13 @@ void set_strip_phase(int phase);
 int launch_pois_residual(const Geo& g, const Coef& c, const double* phi, const double* rp,
                          const double* shift, double* part, hipStream_t st);
 // K5: u = u* - dt grad phi ; min/max partials (4 per block)
-int launch_correct(const Geo& g, const Coef& c, double dt, const double* us, const double* vs, double* u, double* v,
+int launch_correct(const Knobs& kn, const Geo& g, const Coef& c, double dt, const double* us, const double* vs, double* u, double* v,
                    const double* phi, double* part, hipStream_t st);
 // K5 takes the streaming strips here (a rectangle without a NEUMANN side)
-bool correct_streams(const Geo& g);
+bool correct_streams(const Knobs& kn, const Geo& g);
 // K5 + the next step's Poisson guess in the same pass (k_cell_s<6>): gout = gc[0] phi + gc[1] h1
 // + gc[2] h2 + gc[3] h3 (h2 / h3 may be null) -- k_axpby's combination; -1 where K5 does not stream
-int launch_correct_guess(const Geo& g, const Coef& c, double dt, const double* us, const double* vs, double* u,
+int launch_correct_guess(const Knobs& kn, const Geo& g, const Coef& c, double dt, const double* us, const double* vs, double* u,
                          double* v, const double* phi, double* part, const double* h1, const double* h2,
                          const double* h3, const double* gc, double* gout, hipStream_t st);
 // reductions: sum `nv` interleaved values over n partials (p[k*nv + v]) -> out[v]
@@ -216,14 +218,14 @@ void launch_prolong(const Geo& gf, double* phi, const Geo& gc, const double* ec,
 // is null: the coarse level's first pass then takes its iterate as zero without reading it)
 // and partials of r^2 over the fine cells (the MG convergence check); needs 5 ghost rows
 // (none of phi with zin: the input iterate is identically zero and is not read)
-int launch_pois_rbsor2_restrict(const Geo& g, const Coef& c, double omega, const double* phi, double* out,
+int launch_pois_rbsor2_restrict(const Knobs& kn, const Geo& g, const Coef& c, double omega, const double* phi, double* out,
                                 const double* rp, const double* shift, const Geo& gc, double* bc, double* pc,
                                 double* part, hipStream_t st, bool zin = false);
 
 // the same with the input iterate formed on the fly (r4): gcoef[0] phi + gcoef[1] h1 + gcoef[2] h2 +
 // gcoef[3] h3 (h2 / h3 may be null) -- the phi extrapolation, k_axpby's arithmetic; a whole level
 // only (-1 otherwise)
-int launch_pois_rbsor2_restrict_guess(const Geo& g, const Coef& c, double omega, const double* phi, double* out,
+int launch_pois_rbsor2_restrict_guess(const Knobs& kn, const Geo& g, const Coef& c, double omega, const double* phi, double* out,
                                       const double* rp, const double* shift, const Geo& gc, double* bc, double* pc,
                                       double* part, const double* h1, const double* h2, const double* h3,
                                       const double* gcoef, hipStream_t st);
@@ -231,14 +233,14 @@ int launch_pois_rbsor2_restrict_guess(const Geo& g, const Coef& c, double omega,
 // the first post-smoothing pass with the prolongation fused in: phi + P(ec) enters two RB
 // sweeps -> out (phi itself is not modified); needs 5 ghost rows of phi, 3 of ec.  part != null:
 // partials of r^2 of `out` too (the V-cycle's convergence check after its last pass)
-int launch_pois_rbsor2_prolong(const Geo& g, const Coef& c, double omega, const double* phi, double* out,
+int launch_pois_rbsor2_prolong(const Knobs& kn, const Geo& g, const Coef& c, double omega, const double* phi, double* out,
                                const double* rp, const double* shift, const Geo& gc, const double* ec,
                                double* part, hipStream_t st);
 
 // a V-cycle boundary in one pass (k_sweep4, r4): FUSE_P of cycle c and FUSE_R of cycle c + 1 --
 // phi + P(ec) enters four RB sweeps -> out, whose residual is restricted into bc (+ pc := 0 unless
 // null) with r^2 partials; the same values as the two passes.  A whole level (one rank), -1 otherwise
-int launch_pois_sweep4(const Geo& g, const Coef& c, double omega, const double* phi, double* out, const double* rp,
+int launch_pois_sweep4(const Knobs& kn, const Geo& g, const Coef& c, double omega, const double* phi, double* out, const double* rp,
                        const double* shift, const Geo& gc, const double* ec, double* bc, double* pc, double* part,
                        hipStream_t st);
 // the same two passes as LDS-tiled kernels for the latency-bound small levels (one load
@@ -256,7 +258,7 @@ size_t coarse_vcycle_bytes(const Geo& g);
 // solve's matrix; dn = its size, 0 = RB-SOR sweeps); its size in doubles or < 0
 int cv_image(const double* hx, const double* hy, int nx, int ny, int dlo, int dhi, std::vector<double>& img, int* dn);
 // zin: the level's phi is implicitly zero (not read)
-int launch_coarse_vcycle(const Geo& g, const double* img, int img_n, int dn, double* phi, const double* b, int cycles,
+int launch_coarse_vcycle(const Knobs& kn, const Geo& g, const double* img, int img_n, int dn, double* phi, const double* b, int cycles,
                          int pre, int post, int citers, double comega, double somega, int dlo, int dhi,
                          hipStream_t st, int zin = 0);
 // the coarsest level's exact separable solve (k_direct), one stage G = [E o] (P M Q): P n1p x n1p,
@@ -312,7 +314,7 @@ int launch_helm_mt_mask(const Geo& g, const Coef& c, double alpha, double omega,
 void launch_helm_rbt_mask(const Geo& g, const Coef& c, double alpha, double omega, const double* u, const double* v,
                           const double* bu, const double* bv, double* uo, double* vo, hipStream_t st);
 // (stop: a KS_STOP slot -- the grid kernels then do nothing once it is set; null: always run)
-int launch_apply(int op, const Geo& g, const Coef& c, double alpha, const double* x, double* y, const double* q,
+int launch_apply(const Knobs& kn, int op, const Geo& g, const Coef& c, double alpha, const double* x, double* y, const double* q,
                  double* part, hipStream_t st, const double* stop = nullptr);
 // z = q / diag(A) (Jacobi preconditioner of the masked-domain solves)
 void launch_diag_pc(int op, const Geo& g, const Coef& c, double alpha, const double* q, double* z, hipStream_t st,
@@ -408,10 +410,10 @@ int fps_log2(int ny);
 // (r6) the inverse transform writing only the FC_IN cells of `fcm` (a masked domain's solution into phi, the rest
 // of `out` untouched); -1 where unsupported (fps_idct_mask_ok)
 bool fps_idct_mask_ok(int ny);
-bool fps_fuse_ok(int ny, int outE);   // (r6) the divergence fused into the forward transform (launch_fps_div)
-int launch_fps_idct_masked(const double* in, double* out, int nrows, int ny, int ld, const double* tw, const double* wk,
+bool fps_fuse_ok(const Knobs& kn, int ny, int outE);   // (r6) the divergence fused into the forward transform (launch_fps_div)
+int launch_fps_idct_masked(const Knobs& kn, const double* in, double* out, int nrows, int ny, int ld, const double* tw, const double* wk,
                            hipStream_t st, const int32_t* fcm);
-int launch_fps_dct(bool inverse, const double* in, const double* shift, double* out, int nrows, int ny, int ld,
+int launch_fps_dct(const Knobs& kn, bool inverse, const double* in, const double* shift, double* out, int nrows, int ny, int ld,
                    const double* tw, const double* wk, hipStream_t st, int oe_pair = -1, const double* tw8 = nullptr);
 // (r5) log2(ny) also for ny = 16384 (the two-half transforms of launch_fps_dct), else as fps_log2
 int fps_log2x(int ny);
@@ -427,7 +429,7 @@ void launch_dense_mats(const double* C, const double* shy, double rsum, int N, d
 // (sum b, sum b^2) per row pair p at part + 2 p.  phase 0: every row pair; 1: those whose rows need no
 // ghost row of u*; 2: the others (the first and last pair).  Returns the partial count (the pairs), or
 // -1 (ny unsupported)
-int launch_fps_div(const Geo& g, const Coef& c, double dt, const double* u, const double* v, double* b, double* out,
+int launch_fps_div(const Knobs& kn, const Geo& g, const Coef& c, double dt, const double* u, const double* v, double* b, double* out,
                    double* part, int phase, const double* tw, const double* wk, hipStream_t st, int outE = 0);
 void launch_fps_t1(const FpsArgs& a, const double* f, hipStream_t st);
 void launch_fps_t2(const FpsArgs& a, double* f, hipStream_t st);

@@ -4841,20 +4841,19 @@ static hipError_t launch_raw(const void* k, dim3 grid, dim3 block, void** args, 
     return hipLaunchKernel(k, grid, block, args, shmem, st);
 }
 
-static long resident_waves(const void* k);
+static long resident_waves(const Knobs& kn, const void* k);
 static int strip_rows(int nxl, long nsj, long cap, int lmin, int lmax = 64);
 
-int launch_rhs(const Geo& g, const Coef& c, double dt, double re, const double* u, const double* v,
+int launch_rhs(const Knobs& kn, const Geo& g, const Coef& c, double dt, double re, const double* u, const double* v,
                const double* phi, double* cu, double* cv, double* ru, double* rv, double* part, hipStream_t st,
                int depth, double* uo, double* vo, double* mm) {
-    const char* e = getenv("NSGPU_RHS");   // NSGPU_RHS=global: the global-load K1 (A/B)
     // (r6) uo: the previous step's correction folded in (k_rhs_sc) -- the streaming kernel only, rectangles without
     // NEUMANN sides, hy uniform (the solver asks for it only there)
-    if (uo && (e || g.fc || !c.yuni || g.neu[0] || g.neu[1] || g.neu[2] || g.neu[3])) return -1;
+    if (uo && (kn.rhs != Knobs::RHS_STREAM || g.fc || !c.yuni || g.neu[0] || g.neu[1] || g.neu[2] || g.neu[3])) return -1;
     // (the grid kernels cannot split: the interior phase launches nothing, the edge phase all;
     // K1 updates cu / cv in place, so no cell may run twice)
     if (g.fc) {   // masked domain: the grid kernel with the polygon's topology
-        if (e && std::strcmp(e, "global") == 0) {   // (A/B: r1-r4's global-load kernel)
+        if (kn.rhs == Knobs::RHS_GLOBAL) {   // (A/B: r1-r4's global-load kernel)
             const int rows = cell_rows(g);
             const dim3 cg = cell_grid(g, rows);
             if (g_phase != 1)
@@ -4872,7 +4871,7 @@ int launch_rhs(const Geo& g, const Coef& c, double dt, double re, const double* 
         }
         return nb + ne;
     }
-    if (!e) {
+    if (kn.rhs == Knobs::RHS_STREAM) {
         // the streaming inner kernel (k_rhs_s) with its wall ring (extra workgroups of the same launch)
         RhsStreamArgs A{};
         A.g = g; A.c = c; A.dt = dt; A.re = re; A.u = u; A.v = v; A.phi = phi; A.cu = cu; A.cv = cv; A.ru = ru;
@@ -4882,8 +4881,7 @@ int launch_rhs(const Geo& g, const Coef& c, double dt, double re, const double* 
         A.ilo = std::max(0, std::min(2 - g.i0, g.nxl));
         A.ihi = std::max(A.ilo, std::min(g.nx - 2 - g.i0, g.nxl));
         A.nsj = (g.ny + SW - 1) / SW;
-        const char* w3 = getenv("NSGPU_K1S");
-        const int kv = w3 ? std::atoi(w3) : 0;
+        const int kv = kn.k1s;
         // (r5) uniform hy: k_rhs_su, the column tables in SGPRs -- 164 VGPRs, three waves per SIMD, no spill
         // (NSGPU_K1S=32; 33: three rows in flight, spills).  Measured slower (driver form, interleaved:
         // 243-246 us vs k_rhs_s's 230 us; profiles/r05/k1_waves.log): K1 moves its bytes at ~0.8 of the
@@ -4896,11 +4894,10 @@ int launch_rhs(const Geo& g, const Coef& c, double dt, double re, const double* 
         {
             // the fewest rows that keep every strip in ONE resident round (strip_rows caps at 64:
             // 4096^2 at 2 waves / SIMD then left 128 of 2176 strips to a second round)
-            const long nsi = std::max(1L, resident_waves(kk) / A.nsj);
+            const long nsi = std::max(1L, resident_waves(kn, kk) / A.nsj);
             int L = std::min(std::max((int)((g.nxl + nsi - 1) / nsi + 1) & ~1, 8), K1_LMAX);
             // (r6, A/B) NSGPU_K1_L: rows per strip (several resident rounds of shorter strips)
-            static const int k1l = getenv("NSGPU_K1_L") ? std::atoi(getenv("NSGPU_K1_L")) : 0;
-            if (k1l >= 4) L = std::min(k1l & ~1, K1_LMAX);
+            if (kn.k1_l >= 4) L = std::min(kn.k1_l & ~1, K1_LMAX);
             A.nstr = A.nsj * plan_rows(g.nxl, L, depth, &A.P, K1_ESPLIT);   // u, v rows ib-2 .. ie+1
         }
         const bool inner = A.jhi > 2 && A.ihi > A.ilo;
@@ -4931,7 +4928,7 @@ int launch_rhs(const Geo& g, const Coef& c, double dt, double re, const double* 
         }
         return A.nstr + nring;
     }
-    if (std::strcmp(e, "global") != 0) {   // NSGPU_RHS=lds: the LDS-tiled K1 (A/B)
+    if (kn.rhs == Knobs::RHS_LDS) {   // NSGPU_RHS=lds: the LDS-tiled K1 (A/B)
         const int nti = (g.nxl + RT - 1) / RT;
         int tlo, thi0;
         const int nrun = phase_range(g.nxl, RT, nti, 2, &tlo, &thi0);   // MUSCL: rows li0-2 .. li0+RT+1
@@ -4953,9 +4950,9 @@ int launch_rhs(const Geo& g, const Coef& c, double dt, double re, const double* 
 }
 
 template <int K>
-static int launch_cell_s(CellStreamArgs A, hipStream_t st) {
+static int launch_cell_s(const Knobs& kn, CellStreamArgs A, hipStream_t st) {
     A.nsj = (A.g.ny + SW - 1) / SW;
-    const int L = strip_rows(A.g.nxl, A.nsj, resident_waves((const void*)k_cell_s<K>), 4);
+    const int L = strip_rows(A.g.nxl, A.nsj, resident_waves(kn, (const void*)k_cell_s<K>), 4);
     int nstr;
     if (K == 3) {
         // K3's (sum, sum^2) partials set the null-space mean (values, not just a norm): the same
@@ -4976,27 +4973,21 @@ static int launch_cell_s(CellStreamArgs A, hipStream_t st) {
     return nstr;
 }
 
-static bool cell_streaming() {
-    const char* e = getenv("NSGPU_CELL");   // NSGPU_CELL=grid: the thread-per-cell K3 / K5 (A/B)
-    return !(e && std::strcmp(e, "grid") == 0);
-}
 
 // (r6) a masked domain on one rank: the streaming K3 / K5 on its FC_DEEP cells + the listed cells (NSGPU_MASK_CELL=0:
 // the thread-per-cell k_div / k_correct<TopoMask>)
-static bool mask_cell_streams(const Geo& g) {
-    const char* e = getenv("NSGPU_MASK_CELL");   // (read per launch: the tests switch it)
-    const bool on = !(e && std::atoi(e) == 0);
-    return on && g.fc && g.ecell && g.nxl == g.nx && cell_streaming();
+static bool mask_cell_streams(const Knobs& kn, const Geo& g) {
+    return kn.mask_cell && g.fc && g.ecell && g.nxl == g.nx && !kn.cell_grid;
 }
 
-int launch_div(const Geo& g, const Coef& c, double dt, const double* u, const double* v, double* rp, double* part,
+int launch_div(const Knobs& kn, const Geo& g, const Coef& c, double dt, const double* u, const double* v, double* rp, double* part,
                hipStream_t st) {
-    if (cell_streaming() && !g.fc) {
+    if (!kn.cell_grid && !g.fc) {
         CellStreamArgs A{};
         A.g = g; A.c = c; A.dt = dt; A.a0 = u; A.a1 = v; A.o0 = rp; A.part = part;
-        return launch_cell_s<3>(A, st);
+        return launch_cell_s<3>(kn, A, st);
     }
-    if (mask_cell_streams(g)) {
+    if (mask_cell_streams(kn, g)) {
         // (an overlapped exchange's interior phase launches nothing: all of it with the edge phase, whole -- the
         // same launches as without the exchange, so a loopback / slab run matches one rank bit for bit)
         if (g_phase == 1) return 0;
@@ -5004,7 +4995,7 @@ int launch_div(const Geo& g, const Coef& c, double dt, const double* u, const do
         g_phase = 0;
         CellStreamArgs A{};
         A.g = g; A.c = c; A.dt = dt; A.a0 = u; A.a1 = v; A.o0 = rp; A.part = part; A.fc = g.fc;
-        const int n1 = launch_cell_s<3>(A, st);
+        const int n1 = launch_cell_s<3>(kn, A, st);
         const int n2 = (g.necell + 255) / 256;
         NS_LAUNCH(k_div_cells, dim3(n2), dim3(256), 0, st, g, c, dt, u, v, rp, part + 2 * n1);
         g_phase = ph;
@@ -5018,13 +5009,12 @@ int launch_div(const Geo& g, const Coef& c, double dt, const double* u, const do
     return (int)(cg.x * cg.y);
 }
 
-int launch_apply(int op, const Geo& g, const Coef& c, double alpha, const double* x, double* y, const double* q,
+int launch_apply(const Knobs& kn, int op, const Geo& g, const Coef& c, double alpha, const double* x, double* y, const double* q,
                  double* part, hipStream_t st, const double* stop) {
-    const char* ae = getenv("NSGPU_APPLY");   // NSGPU_APPLY=grid: k_apply only (A/B)
-    if (op == 0 && !g.fc && cell_streaming() && !(ae && std::strcmp(ae, "grid") == 0)) {
+    if (op == 0 && !g.fc && !kn.cell_grid && !kn.apply_grid) {
         CellStreamArgs A{};
         A.g = g; A.c = c; A.a0 = x; A.a1 = q; A.o0 = y; A.part = part;
-        return launch_cell_s<7>(A, st);
+        return launch_cell_s<7>(kn, A, st);
     }
     const int rows = cell_rows(g);
     const dim3 cg = cell_grid(g, rows);
@@ -5119,36 +5109,36 @@ void launch_bicg_start(double* sc, double thr, double b2, int maxit, hipStream_t
               std::max(maxit, 0));
 }
 
-bool correct_streams(const Geo& g) {
+bool correct_streams(const Knobs& kn, const Geo& g) {
     // (a NEUMANN side's phi ghost reaches two cells inward: the grid kernel's grad_phi)
-    return cell_streaming() && !g.fc && !(g.neu[0] || g.neu[1] || g.neu[2] || g.neu[3]);
+    return !kn.cell_grid && !g.fc && !(g.neu[0] || g.neu[1] || g.neu[2] || g.neu[3]);
 }
 
-int launch_correct_guess(const Geo& g, const Coef& c, double dt, const double* us, const double* vs, double* u,
+int launch_correct_guess(const Knobs& kn, const Geo& g, const Coef& c, double dt, const double* us, const double* vs, double* u,
                          double* v, const double* phi, double* part, const double* h1, const double* h2,
                          const double* h3, const double* gc, double* gout, hipStream_t st) {
-    if (!correct_streams(g) || !h1 || (h3 && !h2)) return -1;
+    if (!correct_streams(kn, g) || !h1 || (h3 && !h2)) return -1;
     CellStreamArgs A{};
     A.g = g; A.c = c; A.dt = dt; A.a0 = phi; A.a1 = us; A.a2 = vs; A.o0 = u; A.o1 = v; A.part = part;
     A.h1 = h1; A.h2 = h2; A.h3 = h3; A.gout = gout;
     A.gc0 = gc[0]; A.gc1 = gc[1]; A.gc2 = gc[2]; A.gc3 = gc[3];
-    return launch_cell_s<6>(A, st);
+    return launch_cell_s<6>(kn, A, st);
 }
 
-int launch_correct(const Geo& g, const Coef& c, double dt, const double* us, const double* vs, double* u, double* v,
+int launch_correct(const Knobs& kn, const Geo& g, const Coef& c, double dt, const double* us, const double* vs, double* u, double* v,
                    const double* phi, double* part, hipStream_t st) {
-    if (correct_streams(g)) {
+    if (correct_streams(kn, g)) {
         CellStreamArgs A{};
         A.g = g; A.c = c; A.dt = dt; A.a0 = phi; A.a1 = us; A.a2 = vs; A.o0 = u; A.o1 = v; A.part = part;
-        return launch_cell_s<5>(A, st);
+        return launch_cell_s<5>(kn, A, st);
     }
-    if (mask_cell_streams(g)) {
+    if (mask_cell_streams(kn, g)) {
         if (g_phase == 1) return 0;   // (as launch_div)
         const int ph = g_phase;
         g_phase = 0;
         CellStreamArgs A{};
         A.g = g; A.c = c; A.dt = dt; A.a0 = phi; A.a1 = us; A.a2 = vs; A.o0 = u; A.o1 = v; A.part = part; A.fc = g.fc;
-        const int n1 = launch_cell_s<5>(A, st);
+        const int n1 = launch_cell_s<5>(kn, A, st);
         const int n2 = (g.necell + 255) / 256;
         NS_LAUNCH(k_correct_cells, dim3(n2), dim3(256), 0, st, g, c, dt, us, vs, u, v, phi, part + 4 * n1);
         g_phase = ph;
@@ -5175,7 +5165,7 @@ static SweepArgs make_args(const Geo& g, const Coef& c, int TI, int TJ) {
 }
 
 static int g_strip_rows = 0;  // 0 = adaptive
-void set_strip_rows(int L) { g_strip_rows = L >= 4 ? (std::min(L, 64) & ~1) : 0; }
+void set_strip_rows(int L) { g_strip_rows = L; }
 
 // waves of kernel `k` (256-thread workgroups) the whole chip holds at once
 // CUs the compute stream may use (0: all): a multi-rank solver's compute stream leaves a few CUs
@@ -5209,7 +5199,7 @@ void lds_attr_once(const void* kern, int bytes) {
         (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
-static long resident_waves(const void* k) {
+static long resident_waves(const Knobs& kn, const void* k) {
     static std::mutex mu;
     static std::map<std::pair<int, const void*>, int> cache;   // blocks per CU, per device
     int nb = 0, dev = 0;
@@ -5223,7 +5213,7 @@ static long resident_waves(const void* k) {
         } else {
             (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, 256, 0);
             cache[{dev, k}] = nb;
-            if (getenv("NSGPU_VERBOSE")) fprintf(stderr, "nsgpu: %p holds %d blocks/CU x %d CUs\n", k, nb, cus);
+            if (kn.verbose) fprintf(stderr, "nsgpu: %p holds %d blocks/CU x %d CUs\n", k, nb, cus);
         }
     }
     const int n = g_compute_cus > 0 ? std::min(g_compute_cus, cus) : cus;
@@ -5327,9 +5317,9 @@ static int plan_strips2(StreamArgs& a, long cap, int depth, int* nblk, int lmax 
 
 // count_only: return the strip (= partial) count a launch with residual would have, launch nothing
 template <int OP, bool RB>
-static int launch_stream(StreamArgs a, hipStream_t st, bool count_only = false) {
+static int launch_stream(const Knobs& kn, StreamArgs a, hipStream_t st, bool count_only = false) {
     if (count_only) a.part = reinterpret_cast<double*>(1);
-    const long cap = resident_waves(a.part ? (const void*)k_sweep<OP, RB, true> : (const void*)k_sweep<OP, RB, false>);
+    const long cap = resident_waves(kn, a.part ? (const void*)k_sweep<OP, RB, true> : (const void*)k_sweep<OP, RB, false>);
     a.L = strip_rows(a.nxl, a.nsj, cap, 4);
     a.nsi = (a.nxl + a.L - 1) / a.L;
     const int nstr = a.nsj * a.nsi, nblk = (nstr + 3) / 4;
@@ -5339,18 +5329,18 @@ static int launch_stream(StreamArgs a, hipStream_t st, bool count_only = false) 
     return nstr;
 }
 
-int launch_pois_rbsor(const Geo& g, const Coef& c, double omega, const double* phi, double* out,
+int launch_pois_rbsor(const Knobs& kn, const Geo& g, const Coef& c, double omega, const double* phi, double* out,
                       const double* rp, const double* shift, double* part, hipStream_t st) {
-    return launch_stream<0, true>(stream_args(g, c, phi, out, rp, shift, 0.0, omega, part, false), st);
+    return launch_stream<0, true>(kn, stream_args(g, c, phi, out, rp, shift, 0.0, omega, part, false), st);
 }
 
 // two fused red-black sweeps: strips of 120 written columns reading rows ib-4 .. ie+3;
 // with the output residual (part != null) 116 columns, rows ib-5 .. ie+4
 template <int OP>
-static int launch_stream2(StreamArgs a, const Geo& g, hipStream_t st, bool count_only = false) {
+static int launch_stream2(const Knobs& kn, StreamArgs a, const Geo& g, hipStream_t st, bool count_only = false) {
     if (count_only) a.part = reinterpret_cast<double*>(1);
     a.nsj = a.part ? (g.ny + SW2X - 1) / SW2X : (g.ny + SW2 - 1) / SW2;
-    const long cap = resident_waves(a.part ? (const void*)k_sweep2<OP, true, FUSE_NONE>
+    const long cap = resident_waves(kn, a.part ? (const void*)k_sweep2<OP, true, FUSE_NONE>
                                            : (const void*)k_sweep2<OP, false, FUSE_NONE>);
     int nblk = 0;
     const int nstr = plan_strips2(a, cap, a.part ? 5 : 4, &nblk);
@@ -5368,7 +5358,7 @@ static int launch_stream2(StreamArgs a, const Geo& g, hipStream_t st, bool count
     return nstr;
 }
 
-int launch_pois_rbsor2_restrict(const Geo& g, const Coef& c, double omega, const double* phi, double* out,
+int launch_pois_rbsor2_restrict(const Knobs& kn, const Geo& g, const Coef& c, double omega, const double* phi, double* out,
                                 const double* rp, const double* shift, const Geo& gc, double* bc, double* pc,
                                 double* part, hipStream_t st, bool zin) {
     StreamArgs a = stream_args(g, c, phi, out, rp, shift, 0.0, omega, part, false);
@@ -5376,14 +5366,14 @@ int launch_pois_rbsor2_restrict(const Geo& g, const Coef& c, double omega, const
     a.nsj = (g.ny + SW2X - 1) / SW2X;
     int nblk = 0;
     const void* k = zin ? (const void*)k_sweep2<0, false, FUSE_R, true> : (const void*)k_sweep2<0, false, FUSE_R>;
-    const int nstr = plan_strips2(a, resident_waves(k), 5, &nblk);
+    const int nstr = plan_strips2(a, resident_waves(kn, k), 5, &nblk);
     if (!nblk) return nstr;
     if (zin) NS_LAUNCH((k_sweep2<0, false, FUSE_R, true>), dim3(nblk), dim3(256), 0, st, a);
     else NS_LAUNCH((k_sweep2<0, false, FUSE_R>), dim3(nblk), dim3(256), 0, st, a);
     return nstr;
 }
 
-int launch_pois_rbsor2_restrict_guess(const Geo& g, const Coef& c, double omega, const double* phi, double* out,
+int launch_pois_rbsor2_restrict_guess(const Knobs& kn, const Geo& g, const Coef& c, double omega, const double* phi, double* out,
                                       const double* rp, const double* shift, const Geo& gc, double* bc, double* pc,
                                       double* part, const double* h1, const double* h2, const double* h3,
                                       const double* gcoef, hipStream_t st) {
@@ -5394,12 +5384,12 @@ int launch_pois_rbsor2_restrict_guess(const Geo& g, const Coef& c, double omega,
     a.gc0 = gcoef[0]; a.gc1 = gcoef[1]; a.gc2 = gcoef[2]; a.gc3 = gcoef[3];
     a.nsj = (g.ny + SW2X - 1) / SW2X;
     int nblk = 0;
-    const int nstr = plan_strips2(a, resident_waves((const void*)k_sweep2_gin), 5, &nblk);
+    const int nstr = plan_strips2(a, resident_waves(kn, (const void*)k_sweep2_gin), 5, &nblk);
     if (nblk) NS_LAUNCH(k_sweep2_gin, dim3(nblk), dim3(256), 0, st, a);
     return nstr;
 }
 
-int launch_pois_rbsor2_prolong(const Geo& g, const Coef& c, double omega, const double* phi, double* out,
+int launch_pois_rbsor2_prolong(const Knobs& kn, const Geo& g, const Coef& c, double omega, const double* phi, double* out,
                                const double* rp, const double* shift, const Geo& gc, const double* ec,
                                double* part, hipStream_t st) {
     StreamArgs a = stream_args(g, c, phi, out, rp, shift, 0.0, omega, part, false);
@@ -5417,24 +5407,24 @@ int launch_pois_rbsor2_prolong(const Geo& g, const Coef& c, double omega, const 
     // (with the output residual the fine cone is 5 rows too; the coarse one stays at 3)
     if (FP_W4) {
         const void* k = part ? (const void*)k_sweep2_fp4<true> : (const void*)k_sweep2_fp4<false>;
-        const int nstr = plan_strips2(a, resident_waves(k), 5, &nblk);
+        const int nstr = plan_strips2(a, resident_waves(kn, k), 5, &nblk);
         if (nblk && part) NS_LAUNCH((k_sweep2_fp4<true>), dim3(nblk), dim3(256), 0, st, a);
         else if (nblk) NS_LAUNCH((k_sweep2_fp4<false>), dim3(nblk), dim3(256), 0, st, a);
         return nstr;
     }
     if (part) {
-        const int nstr = plan_strips2(a, resident_waves((const void*)k_sweep2<0, true, FUSE_P>), 5, &nblk);
+        const int nstr = plan_strips2(a, resident_waves(kn, (const void*)k_sweep2<0, true, FUSE_P>), 5, &nblk);
         if (nblk) NS_LAUNCH((k_sweep2<0, true, FUSE_P>), dim3(nblk), dim3(256), 0, st, a);
         return nstr;
     }
-    const int nstr = plan_strips2(a, resident_waves((const void*)k_sweep2<0, false, FUSE_P>), 5, &nblk);
+    const int nstr = plan_strips2(a, resident_waves(kn, (const void*)k_sweep2<0, false, FUSE_P>), 5, &nblk);
     if (nblk) NS_LAUNCH((k_sweep2<0, false, FUSE_P>), dim3(nblk), dim3(256), 0, st, a);
     return nstr;
 }
 
 // a V-cycle boundary of a whole level (k_sweep4): phi + P(ec) -> four RB sweeps -> out, the
 // residual of `out` restricted into bc (pc := 0 unless null), r^2 partials; one rank only
-int launch_pois_sweep4(const Geo& g, const Coef& c, double omega, const double* phi, double* out, const double* rp,
+int launch_pois_sweep4(const Knobs& kn, const Geo& g, const Coef& c, double omega, const double* phi, double* out, const double* rp,
                        const double* shift, const Geo& gc, const double* ec, double* bc, double* pc, double* part,
                        hipStream_t st) {
     if (g.nxl != g.nx || g_phase != 0) return -1;
@@ -5443,7 +5433,7 @@ int launch_pois_sweep4(const Geo& g, const Coef& c, double omega, const double* 
     a.ec = ec; a.ncx = gc.nx; a.ncy = gc.ny; a.ci0 = gc.i0; a.dsx = gc.dsx;
     a.nsj = (g.ny + SW4 - 1) / SW4;
     int nblk = 0;
-    const int nstr = plan_strips2(a, resident_waves((const void*)k_sweep4), 9, &nblk, L4_MAX);
+    const int nstr = plan_strips2(a, resident_waves(kn, (const void*)k_sweep4), 9, &nblk, L4_MAX);
     if (nblk) NS_LAUNCH(k_sweep4, dim3(nblk), dim3(256), 0, st, a);
     return nstr;
 }
@@ -5477,9 +5467,9 @@ int launch_pois_tile2_prolong(const Geo& g, const Coef& c, double omega, const d
     return part ? launch_tile2<FUSE_P, true>(a, g, st) : launch_tile2<FUSE_P>(a, g, st);
 }
 
-int launch_pois_rbsor2(const Geo& g, const Coef& c, double omega, const double* phi, double* out,
+int launch_pois_rbsor2(const Knobs& kn, const Geo& g, const Coef& c, double omega, const double* phi, double* out,
                        const double* rp, const double* shift, double* part, hipStream_t st) {
-    return launch_stream2<0>(stream_args(g, c, phi, out, rp, shift, 0.0, omega, part, false), g, st);
+    return launch_stream2<0>(kn, stream_args(g, c, phi, out, rp, shift, 0.0, omega, part, false), g, st);
 }
 
 // one launch of the Helmholtz wall-band relaxation (k_helm_band: 3 RB-SOR sweeps of u and v on
@@ -5528,7 +5518,7 @@ int launch_helm_band(const Geo& g, const Coef& c, double alpha, double omega, co
 }
 
 // three Helmholtz sweeps in one pass (k_sweep3; no residual): which = 1 u, 2 v, 3 both in one launch
-int launch_helm_sweep3(const Geo& g, const Coef& c, double alpha, double omega, const double* u, const double* v,
+int launch_helm_sweep3(const Knobs& kn, const Geo& g, const Coef& c, double alpha, double omega, const double* u, const double* v,
                        double* uo, double* vo, const double* ru, const double* rv, hipStream_t st, int which,
                        double* part) {
     StreamArgs a = stream_args(g, c, which == 2 ? v : u, which == 2 ? vo : uo, which == 2 ? rv : ru, nullptr, alpha,
@@ -5536,15 +5526,14 @@ int launch_helm_sweep3(const Geo& g, const Coef& c, double alpha, double omega, 
     // the batch's last pass with its output residual (7-row cone: 7 ghost rows on slabs); rows in
     // flight: 3 for one field (114 vs 118 us at 4096^2 with 2), (r5) 2 for the two-field launch (its SD3 = 3
     // build spills 40 B per lane: 207 -> 191 us, bench 16,434 -> 16,725; profiles/r05/sd3/); NSGPU_SD3: A/B
-    static const int sd3e = getenv("NSGPU_SD3") ? std::atoi(getenv("NSGPU_SD3")) : 0;
-    const int sd3 = sd3e ? sd3e : (which == 3 ? 2 : 3);
+    const int sd3 = kn.sd3 ? kn.sd3 : (which == 3 ? 2 : 3);
     if (part) {
         a.nsj = (g.ny + SW3R - 1) / SW3R;
         int nblk = 0;
         const void* kr = which == 3 ? (sd3 == 3 ? (const void*)k_sweep3<FUSE_UV, true, 3> : (const void*)k_sweep3<FUSE_UV, true, 2>)
                                     : (sd3 == 3 ? (const void*)k_sweep3<FUSE_NONE, true, 3> : (const void*)k_sweep3<FUSE_NONE, true, 2>);
         // (two fields: half the resident round per field, strips up to L3_MAX rows)
-        const int nstr = plan_strips2(a, resident_waves(kr) / (which == 3 ? 2 : 1), 7, &nblk, L3_MAX);
+        const int nstr = plan_strips2(a, resident_waves(kn, kr) / (which == 3 ? 2 : 1), 7, &nblk, L3_MAX);
         if (which == 2) a.part = part + nstr;   // partials: u at [0, n), v at [n, 2n) (launch_helm_sweep2)
         if (!nblk) return nstr;
         if (which == 3) {
@@ -5558,7 +5547,7 @@ int launch_helm_sweep3(const Geo& g, const Coef& c, double alpha, double omega, 
     a.nsj = (g.ny + SW2X - 1) / SW2X;
     const void* k = which == 3 ? (const void*)k_sweep3<FUSE_UV> : (const void*)k_sweep3<FUSE_NONE>;
     int nblk = 0;
-    const int nstr = plan_strips2(a, resident_waves(k) / (which == 3 ? 2 : 1), 6, &nblk, L3_MAX);
+    const int nstr = plan_strips2(a, resident_waves(kn, k) / (which == 3 ? 2 : 1), 6, &nblk, L3_MAX);
     if (!nblk) return nstr;
     if (which == 3) {
         a.in2 = v; a.out2 = vo; a.b2 = rv;
@@ -5570,7 +5559,7 @@ int launch_helm_sweep3(const Geo& g, const Coef& c, double alpha, double omega, 
     return nstr;
 }
 
-int launch_helm_sweep2(const Geo& g, const Coef& c, double alpha, double omega, const double* u, const double* v,
+int launch_helm_sweep2(const Knobs& kn, const Geo& g, const Coef& c, double alpha, double omega, const double* u, const double* v,
                        double* uo, double* vo, const double* ru, const double* rv, double* part, hipStream_t st,
                        int which) {
     int n = 0;
@@ -5578,16 +5567,16 @@ int launch_helm_sweep2(const Geo& g, const Coef& c, double alpha, double omega, 
         // both components in one launch (the multi-rank pair pass: one launch boundary, and one
         // edge-strip launch after the exchange, instead of two); partials: u at [0, n), v at [n, 2n)
         StreamArgs a = stream_args(g, c, u, uo, ru, nullptr, alpha, omega, part, true);
-        n = launch_stream2<1>(a, g, st, true);   // strip count only
+        n = launch_stream2<1>(kn, a, g, st, true);   // strip count only
         a.in2 = v; a.out2 = vo; a.b2 = rv; a.part2 = part ? part + n : nullptr;
-        return launch_stream2<1>(a, g, st);
+        return launch_stream2<1>(kn, a, g, st);
     }
-    if (which & 1) n = launch_stream2<1>(stream_args(g, c, u, uo, ru, nullptr, alpha, omega, part, true), g, st);
+    if (which & 1) n = launch_stream2<1>(kn, stream_args(g, c, u, uo, ru, nullptr, alpha, omega, part, true), g, st);
     if (which & 2) {
         StreamArgs a = stream_args(g, c, v, vo, rv, nullptr, alpha, omega, nullptr, true);
-        if (!(which & 1)) n = launch_stream2<1>(a, g, st, true);   // strip count only
+        if (!(which & 1)) n = launch_stream2<1>(kn, a, g, st, true);   // strip count only
         a.part = part ? part + n : nullptr;
-        n = launch_stream2<1>(a, g, st);
+        n = launch_stream2<1>(kn, a, g, st);
     }
     return n;
 }
@@ -5595,7 +5584,7 @@ int launch_helm_sweep2(const Geo& g, const Coef& c, double alpha, double omega, 
 
 // -1 if the plane does not fit the kernel's 32-bit buffer offsets
 template <class T>
-static int launch_jacobi_s(const Geo& g, const Coef& c, double omega, const T* in, T* out, const T* rp,
+static int launch_jacobi_s(const Knobs& kn, const Geo& g, const Coef& c, double omega, const T* in, T* out, const T* rp,
                            const double* shift, double* part, hipStream_t st) {
     if ((size_t)(g.nxl + 2 * HALO) * g.ld * sizeof(T) >= (size_t)OOB) return -1;
     JacobiArgs<T> a{};
@@ -5612,7 +5601,7 @@ static int launch_jacobi_s(const Geo& g, const Coef& c, double omega, const T* i
     // strips of at most 24 rows (r4, tools/sweep_c5.py over NSGPU_STRIP_ROWS): past the Infinity Cache
     // one resident round of 64-row strips ran at 0.62 of the HBM peak (8192^2, 16384^2), several
     // rounds of 20-24-row strips at 0.66-0.67; at 4096^2 the one-round height is below 24 anyway
-    a.L = strip_rows(a.nxl, a.nsj, resident_waves(k), 4, 24);
+    a.L = strip_rows(a.nxl, a.nsj, resident_waves(kn, k), 4, 24);
     a.nsi = (a.nxl + a.L - 1) / a.L;
     const int nstr = a.nsj * a.nsi, nblk = (nstr + 3) / 4;
     void* args[] = {&a};
@@ -5620,19 +5609,19 @@ static int launch_jacobi_s(const Geo& g, const Coef& c, double omega, const T* i
     return nstr;
 }
 
-int launch_pois_jacobi(const Geo& g, const Coef& c, double omega, const double* in, double* out, const double* rp,
+int launch_pois_jacobi(const Knobs& kn, const Geo& g, const Coef& c, double omega, const double* in, double* out, const double* rp,
                        const double* shift, double* part, hipStream_t st) {
     // the branch-free streaming sweep; a plane past 4 GiB: k_sweep<Jacobi>
     {
-        const int n = launch_jacobi_s<double>(g, c, omega, in, out, rp, shift, part, st);
+        const int n = launch_jacobi_s<double>(kn, g, c, omega, in, out, rp, shift, part, st);
         if (n >= 0) return n;
     }
-    return launch_stream<0, false>(stream_args(g, c, in, out, rp, shift, 0.0, omega, part, false), st);
+    return launch_stream<0, false>(kn, stream_args(g, c, in, out, rp, shift, 0.0, omega, part, false), st);
 }
 
-int launch_pois_jacobi32(const Geo& g, const Coef& c, double omega, const float* in, float* out, const float* rp,
+int launch_pois_jacobi32(const Knobs& kn, const Geo& g, const Coef& c, double omega, const float* in, float* out, const float* rp,
                          const double* shift, double* part, hipStream_t st) {
-    return launch_jacobi_s<float>(g, c, omega, in, out, rp, shift, part, st);
+    return launch_jacobi_s<float>(kn, g, c, omega, in, out, rp, shift, part, st);
 }
 
 void launch_to_f32(const Geo& g, const double* src, float* dst, hipStream_t st) {
@@ -5644,17 +5633,17 @@ void launch_to_f64(const Geo& g, const float* src, double* dst, hipStream_t st) 
     NS_LAUNCH(k_to_f64, dim3((unsigned)std::min<long>((n + 255) / 256, 8192)), dim3(256), 0, st, src, dst, n);
 }
 
-int launch_helm_sweep(const Geo& g, const Coef& c, double alpha, double omega, const double* u, const double* v,
+int launch_helm_sweep(const Knobs& kn, const Geo& g, const Coef& c, double alpha, double omega, const double* u, const double* v,
                       double* uo, double* vo, const double* ru, const double* rv, double* part, hipStream_t st,
                       int which) {
     // u and v are independent systems with the same operator: two streaming passes
     int n = 0;
-    if (which & 1) n = launch_stream<1, true>(stream_args(g, c, u, uo, ru, nullptr, alpha, omega, part, true), st);
+    if (which & 1) n = launch_stream<1, true>(kn, stream_args(g, c, u, uo, ru, nullptr, alpha, omega, part, true), st);
     if (which & 2) {
         StreamArgs a = stream_args(g, c, v, vo, rv, nullptr, alpha, omega, nullptr, true);
-        if (!(which & 1)) n = launch_stream<1, true>(a, st, true);   // strip count only
+        if (!(which & 1)) n = launch_stream<1, true>(kn, a, st, true);   // strip count only
         a.part = part ? part + n : nullptr;
-        n = launch_stream<1, true>(a, st);
+        n = launch_stream<1, true>(kn, a, st);
     }
     return n;
 }
@@ -5801,7 +5790,7 @@ int cv_image(const double* hx, const double* hy, int nx, int ny, int dlo, int dh
     return n_img;
 }
 
-int launch_coarse_vcycle(const Geo& g, const double* img, int img_n, int dn, double* phi, const double* b, int cycles,
+int launch_coarse_vcycle(const Knobs& kn, const Geo& g, const double* img, int img_n, int dn, double* phi, const double* b, int cycles,
                          int pre, int post, int citers, double comega, double somega, int dlo, int dhi,
                          hipStream_t st, int zin) {
     const size_t bytes = coarse_vcycle_bytes(g);
@@ -5811,8 +5800,7 @@ int launch_coarse_vcycle(const Geo& g, const double* img, int img_n, int dn, dou
     lds_attr_once((const void*)k_coarse_vcycle<true>, 150 * 1024);
     // the 2 x 2-block smoother (every level but the last has even sides; a level of <= 4096 cells
     // fits the LDS, so its blocks fit the workgroup); NSGPU_CV_BLK=0: the cell-loop version (A/B)
-    static const int blk_env = getenv("NSGPU_CV_BLK") ? std::atoi(getenv("NSGPU_CV_BLK")) : 1;
-    const int blk = blk_env && (g.nx / 2) * (g.ny / 2) <= CV_THREADS ? 1 : 0;
+    const int blk = kn.cv_blk && (g.nx / 2) * (g.ny / 2) <= CV_THREADS ? 1 : 0;
     if (blk)
         NS_LAUNCH(k_coarse_vcycle<true>, dim3(1), dim3(CV_THREADS), bytes, st, g, img, img_n, dn, phi, b, cycles, pre,
                   post, citers, comega, somega, dlo, dhi, zin);

@@ -119,6 +119,7 @@ struct MgLevel {
 };
 
 struct ns_solver {
+    nsg::Knobs k;                // the NSGPU_* environment at ns_create (ns_knobs.h): fixed for the solver's life
     nsg::Geo g{};
     nsg::Coef c{};
     int device = 0;
@@ -143,24 +144,14 @@ struct ns_solver {
     int helm_batch0 = 4, pois_batch0 = 8;
     int helm_next = 4;           // first Helmholtz batch of the next step (adaptive unless check_every)
     int helm_adapt = 1;
-    bool triple = true;          // 3-sweep passes allowed on this decomposition (slabs >= 2*HALO rows)
-    bool sweep3 = true;          // single rank: odd Helmholtz batches start with a 3-sweep pass (k_sweep3)
-    bool helm_band = true;       // Helmholtz: wall-band relaxation before the global passes (k_helm_band)
-    // (r6) one rank, 6 band sweeps as ONE k_helm_band6 launch + copy-back (NSGPU_BAND6=1): half the band bytes, but
+    bool triple = true;          // 3-sweep passes allowed on this decomposition
+    // the Helmholtz wall bands (k.helm_band): their width (cells from a wall: min(nx, ny) / 32) and RB-SOR sweeps (a
+    // multiple of 3).  (r6) k.band6, 6 band sweeps as ONE k_helm_band6 launch + copy-back: half the band bytes, but
     // the launches are latency-bound, not HBM-bound -- 100 + 13 us against 2 x 48.5 (profiles/r06/ab/): off
-    bool band6 = false;
-    int band_w = 128, band_sweeps = 6;   // its width (cells from a wall: min(nx, ny) / 32) and RB-SOR sweeps (a multiple of 3)
-    bool sweep3_res = true;      // one rank: a Helmholtz batch may end on a 3-sweep pass with its residual
-    int helm_uv = 1;             // NSGPU_HELM_UV=0: one rank's 3-sweep batch as two one-field launches (A/B)
+    int band_w = 128, band_sweeps = 6;
     int helm_probe = 0;          // steps since the Helmholtz first-pass residual was last sampled
-    int tiled = 0;               // NSGPU_SWEEP=tiled: A/B against the first (LDS-tiled) sweep kernels
-    int fuse_restrict = 1;       // NSGPU_FUSED_RESTRICT=0: separate k_restrict pass (A/B)
-    int fuse_prolong = 1;        // NSGPU_FUSED_PROLONG=0: separate k_prolong pass (A/B)
-    int tile_small = 1;          // NSGPU_TILE_SMALL=0: no LDS-tiled fused passes on small levels (A/B)
-    int ext_timing = 1;          // NSGPU_EXT_TIMING=0: marker events around timed launches (t_begin)
-    int phi_extrap = 3;          // Poisson initial guess: NSGPU_PHI_EXTRAP=0 phi^{n-1}, 1 linear, 2 quadratic,
-                                 // 3 (default) cubic while the last solve took > 1 V-cycle, else quadratic
-    int mg_predict = 1;          // NSGPU_MG_PREDICT=0: a residual check (host sync) after every V-cycle
+    int phi_extrap = 3;          // Poisson initial guess: 0 phi^{n-1}, 1 linear, 2 quadratic, 3 (default) cubic while
+                                 // the last solve took > 1 V-cycle, else quadratic; 0 on a direct solve (choose_paths)
     double mg_rate2 = 0.0;       // last measured per-cycle contraction of ||r||^2
     int mg_hist[4] = {-1, -1, -1, -1};   // V-cycles the last four solves converged at (first check)
     double* phim = nullptr;      // phi^{n-2} (the extrapolation's second point; rotates with PHI / TMP)
@@ -171,8 +162,6 @@ struct ns_solver {
     float* f32_mem = nullptr;    // fp32-field sweep planes (configs[4]), allocated on first use
     float* f32[3] = {};          // phi, its ping-pong partner, rhs_phi (rows of g.ld floats)
     int phim_valid = 0;          // history planes holding data (0 after a reset / an injected phi)
-    int verbose = 0;             // NSGPU_VERBOSE=1: solver residual histories on stderr
-    long pair_min_cells = 2048L * 2048L;   // NSGPU_PAIR_MIN_CELLS: smallest level smoothed in 2-sweep passes
     // multi-rank: ghost-row exchanges of the two-sweep passes run on a comm stream while the
     // pass's interior strips run (NSGPU_OVERLAP=0: exchange, then the whole pass)
     int overlap = 1;
@@ -199,25 +188,22 @@ struct ns_solver {
     double mg_omega_c = 1.0, mg_omega_s = 1.1;
     bool mg_coarse_lds = false;
     // r4: the coarsest level solved exactly by its separable eigen-decomposition (k_direct, two
-    // launches): the first whole coarse level of <= direct_cells cells (NSGPU_DIRECT_CELLS, default
-    // 128^2; 0 = the LDS V-cycle below it as in round 3).  dmat: P1 = Vx^-1, Q1 = Vy^-T, E, P2 = Vx,
+    // launches): the first whole coarse level of <= k.direct_cells cells (default 128^2; 0 = the LDS
+    // V-cycle below it as in round 3).  dmat: P1 = Vx^-1, Q1 = Vy^-T, E, P2 = Vx,
     // Q2 = Vy^T (direct_setup), padded to multiples of 16
-    // r4: a V-cycle boundary on the finest level in one pass (k_sweep4): cycle c's prolongation pass
-    // is deferred when c's output is not checked (p_pending) and runs fused with cycle c+1's
-    // restriction pass.  NSGPU_FUSE4=0: the two passes (A/B, the equivalence test's reference)
-    int fuse4 = 1;
+    // r4: a V-cycle boundary on the finest level in one pass (k_sweep4, k.fuse4): cycle c's prolongation
+    // pass is deferred when c's output is not checked (p_pending) and runs fused with cycle c+1's
+    // restriction pass
     bool p_pending = false;
     // r4: the phi extrapolation formed inside the solve's first restriction pass (k_sweep2_gin) instead
     // of by k_axpby: extrapolate_phi only rotates the planes and leaves the guess's sources here;
     // K3 then runs speculatively behind the Helmholtz check.  Measured (r4, 4096^2 driver form): the
     // pass takes 241 us (184 VGPRs, 2 waves / SIMD, five streams) against FUSE_R 87 + k_axpby 104 us,
-    // 9,924-9,961 vs 9,957-10,143 MLUPS -- so opt-in (NSGPU_GIN=1); default k_axpby (round 3)
-    int gin = 0;
+    // 9,924-9,961 vs 9,957-10,143 MLUPS -- so opt-in (k.gin); default k_axpby (round 3)
     bool gin_pending = false;
     const double* gin_src[4] = {nullptr, nullptr, nullptr, nullptr};
     double gin_c[4] = {0, 0, 0, 0};
     bool mg_direct = false;
-    long direct_cells = 128L * 128L;
     double* dmat = nullptr;
     const double *dP1 = nullptr, *dQ1 = nullptr, *dE = nullptr, *dP2 = nullptr, *dQ2 = nullptr;
     // NEUMANN outflow (pois_solve_krylov): BiCGStab planes r, r0, p, v, s, t, ph, sh, scratch
@@ -281,21 +267,21 @@ struct ns_solver {
     // trip; k5_spec = 1 after a passing check (the step then only swaps), 0 otherwise (K5 runs
     // again after the last cycle: u* is untouched, K5 writes TMPU / TMPV)
     int in_step = 0, k5_spec = 0, n_spec = 0, n_spec_hit = 0;
-    int speculate = 1;           // NSGPU_SPECULATE=0: no speculative K5 / K3 (the equivalence test's reference)
-    // r4: K5 may form the next step's Poisson guess (k_cell_s<6>, NSGPU_K5_GUESS=1; default: k_axpby
+    // (k.speculate = 0: no speculative K5 / K3, the equivalence test's reference)
+    // r4: K5 may form the next step's Poisson guess (k_cell_s<6>, k.k5_guess; default: k_axpby
     // at the next step as in round 3); guess_ready: TMP holds it (branch guess_branch of extrap_plan) -- any entry
     // point that may write TMP or the phi planes clears it.  K3 then runs speculatively behind the
     // Helmholtz residual check (k3_spec: rhs_phi is this step's), which the extrapolation used to fill
     // Measured (r4, 4096^2 driver form): k_cell_s<6> 242 us against K5 128 + k_axpby 104 us -- no gain
-    // (9,819-9,822 vs 9,821-9,863 MLUPS), so it is opt-in (NSGPU_K5_GUESS=1)
-    int k5_guess = 0, guess_ready = 0, guess_branch = 0, k3_spec = 0;
+    // (9,819-9,822 vs 9,821-9,863 MLUPS), so it is opt-in
+    int guess_ready = 0, guess_branch = 0, k3_spec = 0;
     int cur_cycles = -1;         // V-cycles of the Poisson solve in progress (at its K5)
     int last_cycles = -1;        // V-cycles of the last multigrid solve (-1: none / Krylov)
     // r4: the direct Poisson solve (ns_fps.hip) of a rectangle with zero-flux phi sides and uniform hy
     // (ny a power of two): DCT along y, tridiagonal recurrences along x, inverse DCT -- no iteration,
     // so no initial guess (no phi history planes).  Its output residual (a separate pass: 76 us at
-    // 4096^2) is checked on the first solve of a run and every fps_check-th after it (NSGPU_FPS_CHECK,
-    // default 16; 1 = every solve; a standalone ns_kernel solve always); the check's host sync hides
+    // 4096^2) is checked on the first solve of a run and every k.fps_check-th after it (default 16;
+    // 1 = every solve; a standalone ns_kernel solve always); the check's host sync hides
     // behind a speculative K5, and a residual above rtol continues with multigrid V-cycles from this
     // phi.  The solve is a fixed arithmetic sequence: its residual does not drift between checks
     // (1e-13 .. 1e-12 of ||b|| at 4096^2).  NSGPU_FPS=0: multigrid
@@ -309,7 +295,6 @@ struct ns_solver {
     double* fps_mem = nullptr;
     const double *fps_tw = nullptr, *fps_wk = nullptr;
     const double* fps_tw8 = nullptr;   // (r5) ny = 16384: the 8192-point halves' twiddles
-    int fps_check = 16;
     int fps_passes = 2;          // full passes of the tridiagonal recurrences (NSGPU_FPS_PASSES=3: t1 / t2 / t3)
     long fps_solves = 0;
     // multi-rank: this rank's aggregate of a recurrence (2 x ld), every rank's (nranks x 2 x ld, one
@@ -330,11 +315,9 @@ struct ns_solver {
     const double *m0e = nullptr, *m0b = nullptr, *m0g = nullptr, *m0a = nullptr;
     double fps_res = -1.0;       // the last checked solve's relative residual
     int kpred[3] = {1, 1, 1};    // (r5) the last BiCGStab solve's iterations: Poisson, Helmholtz u, v (bicgstab's batch)
-    // (r5) a masked domain's Helmholtz solve on one rank by red-black SOR (NSGPU_MASK_HELM=krylov: BiCGStab); the
-    // sweeps the last step needed (the next step's first batch)
-    bool mask_rb = true, mask_rbt = true;
-    bool mask_mt = true;   // (r6) masked Helmholtz: up to 4 sweeps per launch + the residual in the last (NSGPU_MASK_MT=0: rbt)
-    int mask_band = 6;     // (r6) masked Helmholtz: wall-band sweeps before the global ones (NSGPU_MASK_BAND; 0 off, multiple of 6)
+    // (r5) a masked domain's Helmholtz solve on one rank by red-black SOR (k.mask_rb; k.mask_mt: up to 4 sweeps per
+    // launch + the residual in the last; k.mask_band wall-band sweeps first): the sweeps the last step needed (the
+    // next step's first batch)
     int mask_helm_next = 4, mask_helm_ok = 0;
     // r5, multi-rank rectangles: the Helmholtz check's collective is an allgather of every rank's
     // S_HBNL .. S_MML (bus()): K1's norms and the previous step's K5 min / max ride on it, so neither
@@ -585,7 +568,7 @@ int extrapolate_phi(ns_solver* s);
 // reports).  Multi-rank calls (exchanges, split launches) and NSGPU_EXT_TIMING=0: marker
 // events around the call, which also count the launch's dispatch latency.
 int t_begin(ns_solver* s, hipEvent_t a, hipEvent_t b) {
-    if (s->nranks == 1 && s->ext_timing) {
+    if (s->nranks == 1 && s->k.ext_timing) {
         nsg::time_next_launch(a, b);
         return 0;
     }
@@ -593,7 +576,7 @@ int t_begin(ns_solver* s, hipEvent_t a, hipEvent_t b) {
     return 0;
 }
 int t_end(ns_solver* s, hipEvent_t a, hipEvent_t b) {
-    if (s->nranks == 1 && s->ext_timing) {
+    if (s->nranks == 1 && s->k.ext_timing) {
         if (nsg::time_next_launch_pending()) {   // the call launched no kernel: an empty interval
             HIPCHK(hipEventRecord(a, s->st));
             HIPCHK(hipEventRecord(b, s->st));
@@ -625,7 +608,7 @@ int ensure_events(ns_solver* s, size_t n) {
 // Helmholtz sweeps of the fields in `which` (1 = u, 2 = v, 3 = both): U,V -> TMPU,TMPV, then
 // swap so NS_ARR_U/V stay "current".  Partials: u at part[0, nb), v at part[nb, 2 nb).
 int helm_sweep(ns_solver* s, double alpha, double* part, int which = 3) {
-    const int nb = nsg::launch_helm_sweep(s->g, s->c, alpha, s->omega_v, s->arr[NS_ARR_U], s->arr[NS_ARR_V],
+    const int nb = nsg::launch_helm_sweep(s->k, s->g, s->c, alpha, s->omega_v, s->arr[NS_ARR_U], s->arr[NS_ARR_V],
                                           s->arr[NS_ARR_TMPU], s->arr[NS_ARR_TMPV], s->arr[NS_ARR_RU],
                                           s->arr[NS_ARR_RV], part, s->st, which);
     if (which & 1) std::swap(s->arr[NS_ARR_U], s->arr[NS_ARR_TMPU]);
@@ -647,7 +630,7 @@ int helm_sweep3(ns_solver* s, double alpha, int which, double* part = nullptr) {
         }
         if (t_begin(s, s->hev[2 * s->hn], s->hev[2 * s->hn + 1]) != 0) return -1;
     }
-    const int nb = nsg::launch_helm_sweep3(s->g, s->c, alpha, s->omega_v, s->arr[NS_ARR_U], s->arr[NS_ARR_V],
+    const int nb = nsg::launch_helm_sweep3(s->k, s->g, s->c, alpha, s->omega_v, s->arr[NS_ARR_U], s->arr[NS_ARR_V],
                                            s->arr[NS_ARR_TMPU], s->arr[NS_ARR_TMPV], s->arr[NS_ARR_RU],
                                            s->arr[NS_ARR_RV], s->st, which, part);
     if (nb < 0) return nb;
@@ -674,7 +657,7 @@ int helm_sweep2(ns_solver* s, double alpha, double* part, int which = 3) {
         }
         if (t_begin(s, s->hev[2 * s->hn], s->hev[2 * s->hn + 1]) != 0) return -1;
     }
-    const int nb = nsg::launch_helm_sweep2(s->g, s->c, alpha, s->omega_v, s->arr[NS_ARR_U], s->arr[NS_ARR_V],
+    const int nb = nsg::launch_helm_sweep2(s->k, s->g, s->c, alpha, s->omega_v, s->arr[NS_ARR_U], s->arr[NS_ARR_V],
                                            s->arr[NS_ARR_TMPU], s->arr[NS_ARR_TMPV], s->arr[NS_ARR_RU],
                                            s->arr[NS_ARR_RV], part, s->st, which);
     if (t) {
@@ -700,8 +683,8 @@ int helm_sweeps(ns_solver* s, double alpha, int n, double* part_first, double* p
     int nb = 0;
     // one rank: u's passes, then v's -- or, with helm_uv, a batch of a single 3-sweep residual pass
     // per component as ONE two-field launch (each field's strips twice as long: one resident round)
-    const bool split = s->nranks == 1 && !(s->helm_uv && n == 3 && s->sweep3 && s->triple && s->sweep3_res &&
-                                          !part_first && !s->tiled);
+    const bool split = s->nranks == 1 && !(s->k.helm_uv && n == 3 && s->k.sweep3 && s->triple && s->k.sweep3_res &&
+                                          !part_first && !s->k.tiled);
     for (int which : {split ? 1 : 3, split ? 2 : 0}) {
         if (!which) break;
         int k = 0, launch = 0;
@@ -711,12 +694,12 @@ int helm_sweeps(ns_solver* s, double alpha, int n, double* part_first, double* p
             // 8 = 3+3+2, 11 = 3+3+3+2: a third fewer HBM passes); an odd remainder of >= 3 otherwise
             // starts with a single sweep.  Every pass equals its single sweeps bit for bit, so one
             // rank and slabs agree.  A probing first pass stays a pair (2+3+2)
-            int w = std::min(s->tiled ? 1 : 2, n - k);
-            if (!s->tiled && !(launch == 0 && part_first)) {
+            int w = std::min(s->k.tiled ? 1 : 2, n - k);
+            if (!s->k.tiled && !(launch == 0 && part_first)) {
                 // (a batch may also end on a 3-sweep pass with the residual stage, 7-row cone:
                 // 5 = 3+2, 3 = 3, 6 = 3+3 -- slabs too, with 7 ghost rows)
-                const bool end3 = s->sweep3_res;
-                if (s->sweep3 && s->triple && (n - k >= 5 || (end3 && (n - k == 3 || n - k == 6)))) w = 3;
+                const bool end3 = s->k.sweep3_res;
+                if (s->k.sweep3 && s->triple && (n - k >= 5 || (end3 && (n - k == 3 || n - k == 6)))) w = 3;
                 else if (((n - k) & 1) && n - k >= 3) w = 1;
             }
             const bool last = k + w >= n;
@@ -724,7 +707,7 @@ int helm_sweeps(ns_solver* s, double alpha, int n, double* part_first, double* p
             // iterate ghost rows each pass reads: its cone (3-sweep 6, 2-sweep 4, + 1 with the
             // residual stage; single sweep 2 -- k_sweep reads one, K1 needs two anyway)
             const int hw = w == 3 ? (part ? 7 : 6) : (w == 2 ? (part ? 5 : 4) : 2);
-            if (which == 3 && w >= 2 && !s->tiled) {
+            if (which == 3 && w >= 2 && !s->k.tiled) {
                 // multi-rank pair / triple pass: u and v ghost rows in one exchange, overlapped
                 // (the rhs ghost rows -- 6: the residual 3-sweep pass's first stage -- ride along on
                 // the solve's first pass)
@@ -754,16 +737,16 @@ int helm_sweeps(ns_solver* s, double alpha, int n, double* part_first, double* p
                         int lo = 0;
                         const int ld = s->g.ld;
                         const nsg::Geo gk = deep_geo(s, ex, &lo);
-                        return nsg::launch_helm_sweep3(gk, s->c, alpha, s->omega_v, shp(s->arr[NS_ARR_U], lo, ld),
+                        return nsg::launch_helm_sweep3(s->k, gk, s->c, alpha, s->omega_v, shp(s->arr[NS_ARR_U], lo, ld),
                                                        shp(s->arr[NS_ARR_V], lo, ld), shp(s->arr[NS_ARR_TMPU], lo, ld),
                                                        shp(s->arr[NS_ARR_TMPV], lo, ld), shp(s->arr[NS_ARR_RU], lo, ld),
                                                        shp(s->arr[NS_ARR_RV], lo, ld), s->st, 3, part);
                     }
                     if (w == 3)
-                        return nsg::launch_helm_sweep3(s->g, s->c, alpha, s->omega_v, s->arr[NS_ARR_U], s->arr[NS_ARR_V],
+                        return nsg::launch_helm_sweep3(s->k, s->g, s->c, alpha, s->omega_v, s->arr[NS_ARR_U], s->arr[NS_ARR_V],
                                                        s->arr[NS_ARR_TMPU], s->arr[NS_ARR_TMPV], s->arr[NS_ARR_RU],
                                                        s->arr[NS_ARR_RV], s->st, 3, part);
-                    return nsg::launch_helm_sweep2(s->g, s->c, alpha, s->omega_v, s->arr[NS_ARR_U], s->arr[NS_ARR_V],
+                    return nsg::launch_helm_sweep2(s->k, s->g, s->c, alpha, s->omega_v, s->arr[NS_ARR_U], s->arr[NS_ARR_V],
                                                    s->arr[NS_ARR_TMPU], s->arr[NS_ARR_TMPV], s->arr[NS_ARR_RU],
                                                    s->arr[NS_ARR_RV], part, s->st, 3);
                 };
@@ -804,7 +787,7 @@ int helm_sweeps(ns_solver* s, double alpha, int n, double* part_first, double* p
 // one Poisson sweep PHI -> TMP (RB-SOR or Jacobi), then swap
 int pois_sweep(ns_solver* s, double* part) {
     int nb;
-    if (s->tiled) {
+    if (s->k.tiled) {
         if (s->poisson == NS_POISSON_JACOBI)
             nb = nsg::launch_pois_jacobi_tiled(s->g, s->c, s->omega, s->arr[NS_ARR_PHI], s->arr[NS_ARR_TMP],
                                                s->arr[NS_ARR_RPHI], s->scal + S_SHIFT, part ? part : s->part, s->st);
@@ -812,10 +795,10 @@ int pois_sweep(ns_solver* s, double* part) {
             nb = nsg::launch_pois_rbsor_tiled(s->g, s->c, s->omega, s->arr[NS_ARR_PHI], s->arr[NS_ARR_TMP],
                                               s->arr[NS_ARR_RPHI], s->scal + S_SHIFT, part, s->st);
     } else if (s->poisson == NS_POISSON_JACOBI)
-        nb = nsg::launch_pois_jacobi(s->g, s->c, s->omega, s->arr[NS_ARR_PHI], s->arr[NS_ARR_TMP],
+        nb = nsg::launch_pois_jacobi(s->k, s->g, s->c, s->omega, s->arr[NS_ARR_PHI], s->arr[NS_ARR_TMP],
                                      s->arr[NS_ARR_RPHI], s->scal + S_SHIFT, part ? part : s->part, s->st);
     else
-        nb = nsg::launch_pois_rbsor(s->g, s->c, s->omega, s->arr[NS_ARR_PHI], s->arr[NS_ARR_TMP],
+        nb = nsg::launch_pois_rbsor(s->k, s->g, s->c, s->omega, s->arr[NS_ARR_PHI], s->arr[NS_ARR_TMP],
                                     s->arr[NS_ARR_RPHI], s->scal + S_SHIFT, part, s->st);
     std::swap(s->arr[NS_ARR_PHI], s->arr[NS_ARR_TMP]);
     return nb;
@@ -844,7 +827,7 @@ nsg::Geo f32_view(const ns_solver* s) {
 int pois_sweep32(ns_solver* s, double* part, int* nb) {
     const nsg::Geo v = f32_view(s);
     CHK(halo_g(s, v, {reinterpret_cast<double*>(s->f32[0])}, 1));
-    *nb = nsg::launch_pois_jacobi32(s->g, s->c, s->omega, s->f32[0], s->f32[1], s->f32[2], s->scal + S_SHIFT,
+    *nb = nsg::launch_pois_jacobi32(s->k, s->g, s->c, s->omega, s->f32[0], s->f32[1], s->f32[2], s->scal + S_SHIFT,
                                     part ? part : s->part, s->st);
     if (*nb < 0) { set_err("fp32 Jacobi sweep: launch failed or plane past 4 GiB"); return NS_EINVAL; }
     std::swap(s->f32[0], s->f32[1]);
@@ -931,7 +914,7 @@ int helm_band(ns_solver* s, double alpha) {
     }
     const bool tb = s->timing && s->in_step && s->nranks == 1;   // (r6: the bench's band line)
     if (tb) CHK(ensure_kev(s));
-    if (s->band6 && s->nranks == 1 && rounds == 2) {
+    if (s->k.band6 && s->nranks == 1 && rounds == 2) {
         // (r6) one rank, 6 sweeps: ONE launch of 64 x 64 tiles with their 12-cell cone (k_helm_band6) into the
         // scratch planes, then the band cells' copy-back -- 80 B per band cell instead of 2 x 48 (one timed
         // interval: the bench's band line is the pair)
@@ -984,7 +967,7 @@ int helm_band(ns_solver* s, double alpha) {
 // fewer sweeps than the reference's zero guess.
 int helm_solve(ns_solver* s, int* its, double* resu, double* resv) {
     const double alpha = s->dt / (2 * s->re);
-    if (s->g.fc && s->nranks == 1 && s->mask_rb) {
+    if (s->g.fc && s->nranks == 1 && s->k.mask_rb) {
         // (r5) masked domain, one rank: red-black SOR on I - alpha L_V (strongly diagonally dominant: alpha / h^2 ~ 0.06
         // at 1024^2), u and v sweep by sweep, the residual of both checked after a batch -- the first batch what
         // the previous step needed (NSGPU_MASK_HELM=krylov: the BiCGStab of rounds 1-4)
@@ -993,11 +976,11 @@ int helm_solve(ns_solver* s, int* its, double* resu, double* resv) {
         double bu = 0.0, bv = 0.0;
         int sweeps = 0, batch = std::max(1, s->mask_helm_next);
         double r2u = 0.0, r2v = 0.0;
-        if (s->mask_mt && s->mask_band > 0 && s->mband_n > 0) {
+        if (s->k.mask_mt && s->k.mask_band > 0 && s->mband_n > 0) {
             // (r6) the wall bands first (the residual of the guess u^n lives there, as on the rectangle): launches
             // of 3 sweeps on the FC_BAND cells, U -> TU, then (U, TU) -> U (an even count: the band ends in U)
             const double *RU = s->arr[NS_ARR_RU], *RV = s->arr[NS_ARR_RV];
-            const int nl = s->mask_band / 3;
+            const int nl = s->k.mask_band / 3;
             for (int l = 0; l < nl; l++) {
                 double *U = s->arr[NS_ARR_U], *V = s->arr[NS_ARR_V], *TU = s->arr[NS_ARR_TMPU], *TV = s->arr[NS_ARR_TMPV];
                 const bool odd = l & 1;
@@ -1015,7 +998,7 @@ int helm_solve(ns_solver* s, int* its, double* resu, double* resv) {
             // (r5) whole sweeps in LDS tiles, U, V -> TU, TV -> U, V (an odd batch: its first sweep as the two
             // in-place half-sweeps); NSGPU_MASK_RBT=0: half-sweeps only (A/B)
             double *TU = s->arr[NS_ARR_TMPU], *TV = s->arr[NS_ARR_TMPV];
-            if (s->mask_mt) {
+            if (s->k.mask_mt) {
                 // (r6) up to 4 sweeps per launch (k_helm_mt_mask: LDS temporal blocking), U, V <-> TU, TV, the
                 // batch's last launch with the residuals of both fields -- no pass of its own
                 const int nl = (n + 3) / 4;
@@ -1046,7 +1029,7 @@ int helm_solve(ns_solver* s, int* its, double* resu, double* resv) {
                 continue;
             }
             for (int k = 0; k < n; k++) {
-                if (s->mask_rbt && (n - k) % 2 == 0) {
+                if (s->k.mask_rbt && (n - k) % 2 == 0) {
                     nsg::launch_helm_rbt_mask(s->g, s->c, alpha, s->omega_v, U, V, RU, RV, TU, TV, s->st);
                     nsg::launch_helm_rbt_mask(s->g, s->c, alpha, s->omega_v, TU, TV, RU, RV, U, V, s->st);
                     k++;
@@ -1094,7 +1077,7 @@ int helm_solve(ns_solver* s, int* its, double* resu, double* resv) {
         return 0;
     }
     const double tol2 = s->rtol * s->rtol;
-    if (s->helm_band && !s->tiled) CHK(helm_band(s, alpha));
+    if (s->k.helm_band && !s->k.tiled) CHK(helm_band(s, alpha));
     // first batch: what the previous step needed (consecutive steps converge alike), so a
     // step normally costs one residual check
     int sweeps = 0, batch = s->rp_h > 0 ? s->rp_h : s->helm_next, prev_at = -1;
@@ -1129,12 +1112,12 @@ int helm_solve(ns_solver* s, int* its, double* resu, double* resv) {
         }
         s->hbn_pend = false;
         CHK(fetch_begin(s));
-        if (s->extrap_pending && !s->guess_ready && !(s->gin && gin_ok(s) && s->phim_valid > 0)) {
+        if (s->extrap_pending && !s->guess_ready && !(s->k.gin && gin_ok(s) && s->phim_valid > 0)) {
             // the Poisson initial guess does not depend on u*: it runs on the GPU while the
             // host waits for this check
             s->extrap_pending = 0;
             CHK(extrapolate_phi(s));
-        } else if (s->speculate && s->in_step) {
+        } else if (s->k.speculate && s->in_step) {
             // (r4: K5 formed the guess) K3 instead: the divergence of this batch's u*, v* --
             // the step's rhs_phi if the check passes, formed again after the next batch if not
             CHK(divergence(s));
@@ -1147,7 +1130,7 @@ int helm_solve(ns_solver* s, int* its, double* resu, double* resv) {
         *resu = bu > 0 ? std::sqrt(r2u / bu) : std::sqrt(r2u);
         *resv = bv > 0 ? std::sqrt(r2v / bv) : std::sqrt(r2v);
         if (!std::isfinite(r2u) || !std::isfinite(r2v)) { set_err("Helmholtz residual is not finite"); *its = sweeps; return NS_EDIVERGE; }
-        if (s->verbose) {
+        if (s->k.verbose) {
             if (first)
                 fprintf(stderr, "nsgpu helmholtz: after %d sweeps rel. residual u %.3e v %.3e\n", at0,
                         std::sqrt(s->hs[S_AUX] / std::max(bu, 1e-300)), std::sqrt(s->hs[S_AUX + 1] / std::max(bv, 1e-300)));
@@ -1170,7 +1153,7 @@ int helm_solve(ns_solver* s, int* its, double* resu, double* resv) {
         prev_at = at;
         // even batches (whole 2-sweep passes), or any with the 3-sweep pass (3 + 2 + ... ; a
         // multi-rank odd batch ends with a single sweep: the same count, bit-identical values)
-        batch = std::max(s->sweep3 ? nbatch : nbatch + (nbatch & 1), 2);
+        batch = std::max(s->k.sweep3 ? nbatch : nbatch + (nbatch & 1), 2);
     }
     *its = sweeps;
     // next step's first batch: the sweeps this step's measured contraction says suffice
@@ -1181,7 +1164,7 @@ int helm_solve(ns_solver* s, int* its, double* resu, double* resv) {
         const double more = std::log(tol2 / first_r2) / rate;
         if (std::isfinite(more)) need = std::min(sweeps, first_at + std::max(0, (int)std::ceil(more)));
     }
-    s->helm_next = s->helm_adapt ? std::max(2, s->sweep3 ? need : need + (need & 1)) : s->helm_batch0;
+    s->helm_next = s->helm_adapt ? std::max(2, s->k.sweep3 ? need : need + (need & 1)) : s->helm_batch0;
     // probe again in 8 steps, or on the next step if this one needed more than one batch
     s->helm_probe = (sweeps > n0) ? 0 : (s->helm_probe + 1) % 8;
     return 0;
@@ -1270,9 +1253,9 @@ int flush_b(ns_solver* s, int l) {
 // every rank makes the same choice (the exchange sizes must match).
 bool pair_level(const ns_solver* s, int l) {
     const MgLevel& L = s->lv[l];
-    if (s->tiled) return false;
+    if (s->k.tiled) return false;
     if (s->nranks > 1 && !L.repl) return L.minrows >= nsg::HALO;
-    return (long)L.g.nxl * L.g.ny >= s->pair_min_cells;
+    return (long)L.g.nxl * L.g.ny >= s->k.pair_min_cells;
 }
 
 // the smaller (latency-bound) levels that live whole on this rank run their fused passes as
@@ -1280,20 +1263,20 @@ bool pair_level(const ns_solver* s, int l) {
 // transfers there (A/B)
 bool tile_level(const ns_solver* s, int l) {
     const MgLevel& L = s->lv[l];
-    if (s->tiled || !s->tile_small || pair_level(s, l)) return false;
+    if (s->k.tiled || !s->k.tile_small || pair_level(s, l)) return false;
     return s->nranks == 1 || L.repl;
 }
 
 // the last two pre-smoothing sweeps of level l carry the restriction (k_sweep2<XR> /
 // k_tile2<FUSE_R>); NSGPU_FUSED_RESTRICT=0 keeps the separate k_restrict pass (A/B and tests)
 bool fused_restrict(const ns_solver* s, int l) {
-    return s->fuse_restrict && (pair_level(s, l) || tile_level(s, l)) && s->mg_pre >= 2 && s->mg_pre % 2 == 0;
+    return s->k.fuse_restrict && (pair_level(s, l) || tile_level(s, l)) && s->mg_pre >= 2 && s->mg_pre % 2 == 0;
 }
 
 // the prolongation rides on the first two post-smoothing sweeps (k_sweep2 / k_tile2 FUSE_P);
 // NSGPU_FUSED_PROLONG=0 keeps the separate k_prolong pass
 bool fused_prolong(const ns_solver* s, int l) {
-    return s->fuse_prolong && (pair_level(s, l) || tile_level(s, l)) && s->mg_post >= 2;
+    return s->k.fuse_prolong && (pair_level(s, l) || tile_level(s, l)) && s->mg_post >= 2;
 }
 
 // the finest level's V-cycle boundary may run as one k_sweep4 pass: one rank (the pass reads 9 rows
@@ -1302,14 +1285,14 @@ bool fused_prolong(const ns_solver* s, int l) {
 // also store zeros into it)
 bool zero_ok(const ns_solver* s, int l);
 bool fuse4_level0(const ns_solver* s) {
-    return s->fuse4 && !comm_on(s) && !s->pc_active && s->lv.size() > 1 && !s->lv[0].repl && pair_level(s, 0) &&
+    return s->k.fuse4 && !comm_on(s) && !s->pc_active && s->lv.size() > 1 && !s->lv[0].repl && pair_level(s, 0) &&
            fused_restrict(s, 0) && fused_prolong(s, 0) && s->mg_pre == 2 && s->mg_post == 2 && zero_ok(s, 1);
 }
 
 // the Poisson guess may be formed inside the solve's first level-0 restriction pass (GIN): one rank,
 // the multigrid solve (no Krylov outflow / masked path), its first pass a streaming FUSE_R
 bool gin_ok(const ns_solver* s) {
-    return s->gin && s->in_step && !comm_on(s) && s->poisson == NS_POISSON_MG && !s->kv[0] && !s->g.fc &&
+    return s->k.gin && s->in_step && !comm_on(s) && s->poisson == NS_POISSON_MG && !s->kv[0] && !s->g.fc &&
            s->lv.size() > 1 && !s->lv[0].repl && pair_level(s, 0) && fused_restrict(s, 0) && s->mg_pre == 2;
 }
 
@@ -1414,8 +1397,8 @@ int mg_smooth(ns_solver* s, int l, int n, int* tn, int ev0) {
         const bool t = s->timing && l == 0 && (!s->pc_active || s->pc_timing);
         if (t) { CHK(t_begin(s, s->ev[2 * (ev0 + *tn)], s->ev[2 * (ev0 + *tn) + 1])); s->evtag[ev0 + *tn] = 0; }
         const double* sh = l == 0 ? shift0(s) : nullptr;
-        if (w == 2) nsg::launch_pois_rbsor2(L.g, L.c, s->mg_omega_s, L.phi, L.tmp, L.b, sh, nullptr, s->st);
-        else nsg::launch_pois_rbsor(L.g, L.c, s->mg_omega_s, L.phi, L.tmp, L.b, sh, nullptr, s->st);
+        if (w == 2) nsg::launch_pois_rbsor2(s->k, L.g, L.c, s->mg_omega_s, L.phi, L.tmp, L.b, sh, nullptr, s->st);
+        else nsg::launch_pois_rbsor(s->k, L.g, L.c, s->mg_omega_s, L.phi, L.tmp, L.b, sh, nullptr, s->st);
         if (t) { CHK(t_end(s, s->ev[2 * (ev0 + *tn)], s->ev[2 * (ev0 + *tn) + 1])); (*tn)++; }
         std::swap(L.phi, L.tmp);
         if (l == 0) { s->arr[NS_ARR_PHI] = L.phi; s->arr[NS_ARR_TMP] = L.tmp; }
@@ -1443,7 +1426,7 @@ int mg_coarse(ns_solver* s) {
     if (s->mg_coarse_lds) {
         const int zin = L.zero ? 1 : 0;
         L.zero = false;
-        if (nsg::launch_coarse_vcycle(L.g, s->cvimg, s->cv_n, s->cv_dn, L.phi, L.b, 1, s->mg_pre, s->mg_post,
+        if (nsg::launch_coarse_vcycle(s->k, L.g, s->cvimg, s->cv_n, s->cv_dn, L.phi, L.b, 1, s->mg_pre, s->mg_post,
                                       s->mg_coarse_iters, s->mg_omega_c, s->mg_omega_s, s->out_side == 0,
                                       s->out_side == 1, s->st, zin) != 0) {
             set_err("coarse LDS V-cycle does not fit");
@@ -1454,7 +1437,7 @@ int mg_coarse(ns_solver* s) {
     CHK(zero_phi(s, l));
     for (int k = 0; k < s->mg_coarse_iters; k++) {
         CHK(halo_l(s, l, {L.phi}, 2));
-        nsg::launch_pois_rbsor(L.g, L.c, s->mg_omega_c, L.phi, L.tmp, L.b, nullptr, nullptr, s->st);
+        nsg::launch_pois_rbsor(s->k, L.g, L.c, s->mg_omega_c, L.phi, L.tmp, L.b, nullptr, nullptr, s->st);
         std::swap(L.phi, L.tmp);
     }
     return 0;
@@ -1488,7 +1471,7 @@ int mg_vcycle(ns_solver* s, int* tn, int ev0, Check&& check, bool want_check, bo
             s->gin_pending = false;
             const bool t = s->timing && (!s->pc_active || s->pc_timing);
             if (t) { CHK(t_begin(s, s->ev[2 * (ev0 + *tn)], s->ev[2 * (ev0 + *tn) + 1])); s->evtag[ev0 + *tn] = 3; }
-            nb = nsg::launch_pois_rbsor2_restrict_guess(F.g, F.c, s->mg_omega_s, s->gin_src[0], F.phi, F.b, sh, cv.g,
+            nb = nsg::launch_pois_rbsor2_restrict_guess(s->k, F.g, F.c, s->mg_omega_s, s->gin_src[0], F.phi, F.b, sh, cv.g,
                                                         cv.b, pcz, s->part, s->gin_src[1], s->gin_src[2],
                                                         s->gin_src[3], s->gin_c, s->st);
             if (nb < 0) { set_err("guess restriction pass does not fit"); return NS_EINVAL; }
@@ -1499,7 +1482,7 @@ int mg_vcycle(ns_solver* s, int* tn, int ev0, Check&& check, bool want_check, bo
             s->p_pending = false;
             const bool t = s->timing && (!s->pc_active || s->pc_timing);
             if (t) { CHK(t_begin(s, s->ev[2 * (ev0 + *tn)], s->ev[2 * (ev0 + *tn) + 1])); s->evtag[ev0 + *tn] = 2; }
-            nb = nsg::launch_pois_sweep4(F.g, F.c, s->mg_omega_s, F.phi, F.tmp, F.b, sh, cv.g, cv.phi, cv.b, nullptr,
+            nb = nsg::launch_pois_sweep4(s->k, F.g, F.c, s->mg_omega_s, F.phi, F.tmp, F.b, sh, cv.g, cv.phi, cv.b, nullptr,
                                          s->part, s->st);
             if (nb < 0) { set_err("V-cycle boundary pass does not fit"); return NS_EINVAL; }
             if (t) { CHK(t_end(s, s->ev[2 * (ev0 + *tn)], s->ev[2 * (ev0 + *tn) + 1])); (*tn)++; }
@@ -1518,7 +1501,7 @@ int mg_vcycle(ns_solver* s, int* tn, int ev0, Check&& check, bool want_check, bo
                 nb = nsg::launch_pois_tile2_restrict(F.g, F.c, s->mg_omega_s, F.phi, F.tmp, F.b, sh, cv.g, cv.b, pcz,
                                                      s->part, s->st, zin);
             } else if (F.repl) {
-                nb = nsg::launch_pois_rbsor2_restrict(F.g, F.c, s->mg_omega_s, F.phi, F.tmp, F.b, sh, cv.g, cv.b,
+                nb = nsg::launch_pois_rbsor2_restrict(s->k, F.g, F.c, s->mg_omega_s, F.phi, F.tmp, F.b, sh, cv.g, cv.b,
                                                       pcz, s->part, s->st, zin);
             } else {
                 // (the level's rhs ghost rows ride along when owed; a zero iterate has none to send)
@@ -1527,7 +1510,7 @@ int mg_vcycle(ns_solver* s, int* tn, int ev0, Check&& check, bool want_check, bo
                 const int nr = zin ? (F.b_pend ? 1 : 0) : (F.b_pend ? 2 : 1);
                 F.b_pend = false;
                 auto pass = [&]() {
-                    return nsg::launch_pois_rbsor2_restrict(F.g, F.c, s->mg_omega_s, F.phi, F.tmp, F.b, sh, cv.g,
+                    return nsg::launch_pois_rbsor2_restrict(s->k, F.g, F.c, s->mg_omega_s, F.phi, F.tmp, F.b, sh, cv.g,
                                                             cv.b, pcz, s->part, s->st, zin);
                 };
                 nb = nr ? overlapped(s, rq, nr, pass) : pass();
@@ -1577,8 +1560,10 @@ int mg_vcycle(ns_solver* s, int* tn, int ev0, Check&& check, bool want_check, bo
             // the finest level's last pass also sums its output residual (the convergence check)
             double* pp = (l == 0 && want_check && s->mg_post == 2) ? s->part : nullptr;
             auto pass = [&]() {
-                return (tile_level(s, l) ? nsg::launch_pois_tile2_prolong : nsg::launch_pois_rbsor2_prolong)(
-                    F.g, F.c, s->mg_omega_s, F.phi, F.tmp, F.b, shp, cv.g, cv.phi, pp, s->st);
+                return tile_level(s, l)
+                    ? nsg::launch_pois_tile2_prolong(F.g, F.c, s->mg_omega_s, F.phi, F.tmp, F.b, shp, cv.g, cv.phi, pp, s->st)
+                    : nsg::launch_pois_rbsor2_prolong(s->k, F.g, F.c, s->mg_omega_s, F.phi, F.tmp, F.b, shp, cv.g, cv.phi,
+                                                      pp, s->st);
             };
             if (t) { CHK(t_begin(s, s->ev[2 * (ev0 + *tn)], s->ev[2 * (ev0 + *tn) + 1])); s->evtag[ev0 + *tn] = 0; }
             int n;
@@ -1642,7 +1627,7 @@ int pois_solve_mg(ns_solver* s, int* its, double* res, ns_stats* stt) {
     // steps converge alike, so the check after cycle 0 would only measure a rate already known;
     // a solve converging earlier than all four costs at most that many partial cycles)
     int next_chk = 0, prev_c = -1;
-    if (s->mg_predict && s->mg_rate2 > 0) {
+    if (s->k.mg_predict && s->mg_rate2 > 0) {
         int m = 1 << 30;
         for (int h : s->mg_hist) m = std::min(m, h);
         if (m > 0) next_chk = m;
@@ -1650,7 +1635,7 @@ int pois_solve_mg(ns_solver* s, int* its, double* res, ns_stats* stt) {
     double prev_rr = -1.0;
     if (s->rp_c >= 0) next_chk = s->rp_c;   // virtual slab: the replayed cycle count, one check
     // speculate at the first check when the last four solves all converged by then
-    const bool spec_ok = s->speculate && s->in_step && !s->defer_now && s->mg_predict && s->rp_c < 0 && next_chk > 0;
+    const bool spec_ok = s->k.speculate && s->in_step && !s->defer_now && s->k.mg_predict && s->rp_c < 0 && next_chk > 0;
     auto check = [&](int nb) -> int {
         const int cycles = cyc + 1;   // complete cycles (this check ends one)
         if (!(cycles >= next_chk || cycles >= maxc)) return 0;
@@ -1687,13 +1672,13 @@ int pois_solve_mg(ns_solver* s, int* its, double* res, ns_stats* stt) {
         }
         const double r2 = s->hs[S_RES], b2 = s->hs[S_SHIFT + 1];
         *res = b2 > 0 ? std::sqrt(r2 / b2) : std::sqrt(r2);
-        if (s->verbose) fprintf(stderr, "nsgpu poisson: after %d V-cycles rel. residual %.3e\n", cycles, *res);
+        if (s->k.verbose) fprintf(stderr, "nsgpu poisson: after %d V-cycles rel. residual %.3e\n", cycles, *res);
         if (!std::isfinite(r2)) { set_err("Poisson residual is not finite"); *its = cycles; return NS_EDIVERGE; }
         if (r2 <= tol2 * b2 || r2 == 0.0 || cycles >= maxc || s->rp_c >= 0) {
             if (spec) { s->k5_spec = 1; s->n_spec_hit++; }
             return 1;
         }
-        if (s->mg_predict) {
+        if (s->k.mg_predict) {
             const double rr = r2 / b2;
             double rate = s->mg_rate2;   // per-cycle contraction of r^2
             if (prev_rr > 0 && rr < prev_rr && cycles > prev_c)
@@ -1813,7 +1798,7 @@ int fps_scan(ns_solver* s, bool backward);
 int fps_precond(ns_solver* s, const double* q, double* z, double* scratch, const int32_t* omask = nullptr) {
     const nsg::Geo& g = s->g;
     // ((r5) a masked domain whose box has the E outflow: its row pair transformed eliminated, as the channel's)
-    if (nsg::launch_fps_dct(false, q, nullptr, scratch, g.nxl, g.ny, g.ld, s->fps_tw, s->fps_wk, s->st,
+    if (nsg::launch_fps_dct(s->k, false, q, nullptr, scratch, g.nxl, g.ny, g.ld, s->fps_tw, s->fps_wk, s->st,
                             s->fa.outE ? g.nxl / 2 - 1 : -1) < 0) {
         set_err("direct Poisson preconditioner: ny = %d is not a supported power of two", g.ny);
         return NS_EINVAL;
@@ -1824,13 +1809,13 @@ int fps_precond(ns_solver* s, const double* q, double* z, double* scratch, const
     CHK(fps_scan(s, true));
     nsg::launch_fps_t2b(s->fa, scratch, s->st);
     if (omask) {   // (r6: z's masked-domain cells only)
-        if (nsg::launch_fps_idct_masked(scratch, z, g.nxl, g.ny, g.ld, s->fps_tw, s->fps_wk, s->st, omask) < 0) {
+        if (nsg::launch_fps_idct_masked(s->k, scratch, z, g.nxl, g.ny, g.ld, s->fps_tw, s->fps_wk, s->st, omask) < 0) {
             set_err("direct Poisson preconditioner: no masked inverse transform for ny = %d", g.ny);
             return NS_EINVAL;
         }
         return 0;
     }
-    nsg::launch_fps_dct(true, scratch, nullptr, z, g.nxl, g.ny, g.ld, s->fps_tw, s->fps_wk, s->st);
+    nsg::launch_fps_dct(s->k, true, scratch, nullptr, z, g.nxl, g.ny, g.ld, s->fps_tw, s->fps_wk, s->st);
     return 0;
 }
 
@@ -1861,10 +1846,8 @@ int cap_solve(ns_solver* s, double* q, double* z, double* xout = nullptr) {
 // NSGPU_CAP=0, a Gauss-Jordan pivot that is not finite, below 1e-12 in magnitude, or (no border) not positive
 int cap_setup(ns_solver* s, const ns_grid_desc* gd, const double* pw, const double* pe, const double* ps,
               const double* pn) {
-    const char* ce = getenv("NSGPU_CAP");
-    if (ce && std::atoi(ce) == 0) return 0;
-    const char* cm = getenv("NSGPU_CAP_MAX");
-    const long mmax = std::min(cm ? std::atol(cm) : 4096L, (long)nsg::CAP_LDS_MAX - 1);   // (+ the border row)
+    if (!s->k.cap) return 0;
+    const long mmax = std::min(s->k.cap_max, (long)nsg::CAP_LDS_MAX - 1);   // (+ the border row)
     const nsg::Geo& g = s->g;
     const int nx = gd->nx, ny = gd->ny;
     auto inside = [&](int i, int j) { return gd->cell_id[(size_t)i * ny + j] >= 0; };
@@ -1943,7 +1926,7 @@ int cap_setup(ns_solver* s, const ns_grid_desc* gd, const double* pw, const doub
     HIPCHK(hipMemcpyAsync(&fl, flag, sizeof(double), hipMemcpyDeviceToHost, s->st));
     HIPCHK(hipStreamSynchronize(s->st));
     if (fl != 0.0) {   // (never seen: the preconditioned BiCGStab instead)
-        if (s->verbose)
+        if (s->k.verbose)
             fprintf(stderr, "nsgpu: capacitance matrix (%d faces): a Gauss-Jordan pivot failed the test of k_gj_prep "
                             "(not finite, tiny%s): BiCGStab\n", m, border ? "" : " or not positive");
         s->cap = nsg::CapArgs{};
@@ -1951,7 +1934,7 @@ int cap_setup(ns_solver* s, const ns_grid_desc* gd, const double* pw, const doub
         s->cap_mem = nullptr;
         return 0;
     }
-    if (s->verbose)
+    if (s->k.verbose)
         fprintf(stderr, "nsgpu: masked Poisson by the capacitance matrix: %d interface faces, %d cells%s\n", m, nc,
                 border ? ", bordered (E outflow)" : "");
     return 0;
@@ -1988,7 +1971,7 @@ int bicgstab(ns_solver* s, const KrylovSolve& ks, int* its, double* res) {
     // apply always runs
     auto apply = [&](double* x, double* y, const double* q, bool gate = true) -> int {
         CHK(halo(s, {x}, 1));
-        const int nb = nsg::launch_apply(ks.op, s->g, s->c, ks.alpha, x, y, q, s->part, s->st, gate ? stop : nullptr);
+        const int nb = nsg::launch_apply(s->k, ks.op, s->g, s->c, ks.alpha, x, y, q, s->part, s->st, gate ? stop : nullptr);
         return reduce(nb, 2);
     };
     // timed level-0 passes of the preconditioner (events 0 .. tn), read after each host sync
@@ -2033,7 +2016,7 @@ int bicgstab(ns_solver* s, const KrylovSolve& ks, int* its, double* res) {
     // the gated Helmholtz solves; then 1 (Poisson) or 2 (Helmholtz) at a time.  NSGPU_VERBOSE: every iteration
     const int kind = ks.op == 0 ? 0 : (ks.x == s->arr[NS_ARR_U] ? 1 : 2);
     const bool gated = !ks.mg;
-    int batch = s->verbose ? 1 : std::max(1, gated ? s->kpred[kind] + 1 : s->kpred[kind] - 1);
+    int batch = s->k.verbose ? 1 : std::max(1, gated ? s->kpred[kind] + 1 : s->kpred[kind] - 1);
     double kb2 = ks.b2;   // (< 0: not read yet -- the capacitance solve reads it with its residual)
     nsg::launch_bicg_start(s->ksc, tol2 * kb2, kb2, maxit, s->st);
     int its0 = 0;   // (the capacitance solve's refinements before any BiCGStab iteration)
@@ -2070,7 +2053,7 @@ int bicgstab(ns_solver* s, const KrylovSolve& ks, int* its, double* res) {
             const double r2 = s->hs[S_KRY], b2 = kb2;
             *res = b2 > 0 ? std::sqrt(r2 / b2) : std::sqrt(r2);
             *its = its0;
-            if (s->verbose)
+            if (s->k.verbose)
                 fprintf(stderr, "nsgpu %s (capacitance solve): refinement %d rel. residual %.3e\n", ks.name, its0, *res);
             if (!std::isfinite(r2) || (b2 > 0 && r2 > 1e16 * b2)) {
                 set_err("%s (capacitance solve) diverged: relative residual %g", ks.name, *res);
@@ -2098,7 +2081,7 @@ int bicgstab(ns_solver* s, const KrylovSolve& ks, int* its, double* res) {
         HIPCHK(hipMemcpyAsync(s->scal + S_KRY + 1, s->ksc + nsg::KS_BRK, sizeof(double), hipMemcpyDeviceToDevice, s->st));
         HIPCHK(hipMemcpyAsync(s->scal + S_KRY + 2, s->ksc + nsg::KS_IT, sizeof(double), hipMemcpyDeviceToDevice, s->st));
         HIPCHK(hipMemcpyAsync(s->scal + S_KRY + 3, s->ksc + nsg::KS_R2, sizeof(double), hipMemcpyDeviceToDevice, s->st));
-        if (s->verbose) {
+        if (s->k.verbose) {
             HIPCHK(hipMemcpyAsync(s->scal + S_KRY + 4, d, sizeof(double), hipMemcpyDeviceToDevice, s->st));
             HIPCHK(hipMemcpyAsync(s->scal + S_KRY + 5, s->ksc + nsg::KS_ALPHA, 2 * sizeof(double), hipMemcpyDeviceToDevice, s->st));
         }
@@ -2114,12 +2097,12 @@ int bicgstab(ns_solver* s, const KrylovSolve& ks, int* its, double* res) {
         const int it = (int)s->hs[S_KRY + 2];
         const double r2 = stopped ? s->hs[S_KRY + 3] : s->hs[S_KRY + 4], b2 = kb2;
         *res = b2 > 0 ? std::sqrt(r2 / b2) : std::sqrt(r2);
-        if (s->verbose)
+        if (s->k.verbose)
             fprintf(stderr, "nsgpu %s (bicgstab): it %d rel. residual %.3e (alpha %.3e omega %.3e%s)\n", ks.name, it,
                     *res, s->hs[S_KRY + 5], s->hs[S_KRY + 6], brk ? ", breakdown: restart" : "");
         *its = its0 + it;
         if (!stopped) {
-            batch = s->verbose ? 1 : (gated ? 2 : 1);
+            batch = s->k.verbose ? 1 : (gated ? 2 : 1);
             continue;
         }
         if (!std::isfinite(r2) || (b2 > 0 && r2 > 1e16 * b2)) {
@@ -2166,8 +2149,7 @@ int allgather(ns_solver* s, const double* mine, double* all, size_t n) {
         // the slot filled by a device copy instead -- the 1-rank RCCL kernel of a 131 KB allgather runs on one
         // workgroup for ~60 us, a loopback artefact that tools/slab_projection.py's per-collective cost would
         // count twice)
-        static const bool vcopy = getenv("NSGPU_VIRTUAL_COPY") && std::atoi(getenv("NSGPU_VIRTUAL_COPY")) != 0;
-        if (vcopy) HIPCHK(hipMemcpyAsync(all + r * n, mine, n * 8, hipMemcpyDeviceToDevice, s->st));
+        if (s->k.virtual_copy) HIPCHK(hipMemcpyAsync(all + r * n, mine, n * 8, hipMemcpyDeviceToDevice, s->st));
         else NCCLCHK(ncclAllGather(mine, all + r * n, n, ncclDouble, s->comm, s->st));
         return 0;
     }
@@ -2310,7 +2292,7 @@ int pois_solve_fps(ns_solver* s, int* its, double* res, ns_stats* stt) {
         }
         if (t) HIPCHK(hipEventRecord(s->kev[3], s->st));
         fa.sh0 = fa1.sh0 = fam.sh0 = s->scal + S_SHIFT;
-    } else if (!pre && nsg::launch_fps_dct(false, s->arr[NS_ARR_RPHI], oe ? nullptr : s->scal + S_SHIFT, F, g.nxl, g.ny,
+    } else if (!pre && nsg::launch_fps_dct(s->k, false, s->arr[NS_ARR_RPHI], oe ? nullptr : s->scal + S_SHIFT, F, g.nxl, g.ny,
                                            g.ld, s->fps_tw, s->fps_wk, s->st, oe_pair, s->fps_tw8) < 0) {
         set_err("direct Poisson solve: ny = %d is not a supported power of two", g.ny);
         return NS_EINVAL;
@@ -2363,7 +2345,7 @@ int pois_solve_fps(ns_solver* s, int* its, double* res, ns_stats* stt) {
             return NS_EHIP;
         }
     } else {
-        nsg::launch_fps_dct(true, F - (ptrdiff_t)glo * g.ld, nullptr, s->arr[NS_ARR_PHI] - (ptrdiff_t)glo * g.ld,
+        nsg::launch_fps_dct(s->k, true, F - (ptrdiff_t)glo * g.ld, nullptr, s->arr[NS_ARR_PHI] - (ptrdiff_t)glo * g.ld,
                             g.nxl + glo + ghi, g.ny, g.ld, s->fps_tw, s->fps_wk, s->st, -1, s->fps_tw8);
     }
     if (t) {
@@ -2397,7 +2379,7 @@ int pois_solve_fps(ns_solver* s, int* its, double* res, ns_stats* stt) {
         // with A the reference's matrix (k_apply: the outflow rows' 2.5 / -2 / 0.5 ghost) and P the mean
         // projection; into S_RES through (sum r, sum r^2) and k_finish_mean's ||r - mean r||^2 (one rank)
         double* y = s->kv[0];
-        nsg::launch_apply(0, g, s->c, 0.0, s->arr[NS_ARR_PHI], y, nullptr, s->part, s->st);
+        nsg::launch_apply(s->k, 0, g, s->c, 0.0, s->arr[NS_ARR_PHI], y, nullptr, s->part, s->st);
         nsg::launch_axpby(g, 1.0, s->arr[NS_ARR_RPHI], -1.0, y, y, s->st);
         // (r6) in two passes: the mean off r first, then the sums of r - mean -- the one-pass s2 - s^2 / n cancels
         // when r carries a large constant (the projected system's C 1): 5.7e-10 of noise for a ~1e-14 residual at
@@ -2416,7 +2398,7 @@ int pois_solve_fps(ns_solver* s, int* its, double* res, ns_stats* stt) {
         nsg::launch_reduce_sum(s->part, nb, 1, s->scal + S_RES, s->st);
         CHK(allreduce(s, s->scal + S_RES, 1, ncclSum));
     }
-    const bool spec = s->speculate && s->in_step && !s->defer_now;
+    const bool spec = s->k.speculate && s->in_step && !s->defer_now;
     if (spec) {
         CHK(fetch_begin(s));
         CHK(correct_launch(s, s->part + 4 * (size_t)nsg::max_partials(s->g)));
@@ -2429,7 +2411,7 @@ int pois_solve_fps(ns_solver* s, int* its, double* res, ns_stats* stt) {
     CHK(take_times());
     const double r2 = s->hs[S_RES], b2 = s->hs[S_SHIFT + 1];
     *res = s->fps_res = b2 > 0 ? std::sqrt(r2 / b2) : std::sqrt(r2);
-    if (s->verbose) fprintf(stderr, "nsgpu poisson: direct solve, rel. residual %.3e\n", *res);
+    if (s->k.verbose) fprintf(stderr, "nsgpu poisson: direct solve, rel. residual %.3e\n", *res);
     if (!std::isfinite(r2)) { set_err("Poisson residual is not finite"); return NS_EDIVERGE; }
     // (a virtual slab's own residual is not the global solve's: it replays, never falls back)
     if (r2 <= s->rtol * s->rtol * b2 || r2 == 0.0 || s->rp_c >= 0) {
@@ -2495,10 +2477,7 @@ int fps_setup(ns_solver* s, const std::vector<double>& hy, const double* pw, con
     const size_t n_tab = 4 * (size_t)N + (size_t)N, n_rp0 = (size_t)nchp * ld, n_g = (size_t)a.ngrp * ld;
     // multi-rank: the allgather's own slot and every rank's (fps_n each), and the deferred mean's mode-0
     // tables (chunks' E and BXl, groups', ranks' aggregates of the constant 1)
-    {
-        const char* e = getenv("NSGPU_FPS_ONEGATHER");
-        s->fps_og = s->nranks > 1 && s->nranks <= 64 && s->fps_passes != 3 && !(e && std::atoi(e) == 0);
-    }
+    s->fps_og = s->nranks > 1 && s->nranks <= 64 && s->fps_passes != 3 && s->k.fps_onegather;
     s->fps_n = (s->fps_og ? 4 : 2) * (size_t)ld + 8;
     const size_t n_og = s->fps_og ? (size_t)s->nranks * ld + s->nranks : 0;
     const size_t n_mr = s->nranks > 1 ? (size_t)(1 + s->nranks) * s->fps_n + 2 * (size_t)nchp + a.ngrp + s->nranks + n_og
@@ -2607,8 +2586,7 @@ int fps_setup(ns_solver* s, const std::vector<double>& hy, const double* pw, con
     int prow = 0, kfast = 1 << 30;
     {
         // NSGPU_FPS_PTAB: 0 divisions everywhere, 1 the table (A/B), 2 (default) per 128-mode block its fixed-point row
-        const char* pe_env = getenv("NSGPU_FPS_PTAB");
-        const int mode = !s->fps_xuni || s->fps_dense ? 0 : pe_env ? std::atoi(pe_env) : 2;   // (r6: stretched -- none)
+        const int mode = !s->fps_xuni || s->fps_dense ? 0 : s->k.fps_ptab;   // (r6: stretched -- none)
         const int PRMAX = std::min(g.nx - 1, mode == 1 ? 1024 : 4096);
         if (mode != 0 && N > 128 && PRMAX > 64) {
             std::vector<double> rr(N, 0.0);
@@ -3026,14 +3004,13 @@ int build_levels(ns_solver* s, const std::vector<double>& hx0, const std::vector
     }
     L0.minrows = *std::min_element(rn.begin(), rn.end());
     s->lv.push_back(L0);
-    long agg_cells = 1024L * 1024L;
-    if (const char* e = getenv("NSGPU_AGG_CELLS")) agg_cells = std::atol(e);
+    const long agg_cells = s->k.agg_cells;
     const int agg_min_rows = 8;
     // stop at the first whole coarse level the exact separable solve takes (<= direct_cells, sides
     // <= 128: nsg::direct_fits), else (NSGPU_DIRECT_CELLS=0) at the first whose LDS V-cycle fits (<= ~64^2)
     const size_t lds_cap = 150 * 1024;
     auto direct_fits = [&](const nsg::Geo& g) {
-        return s->direct_cells > 0 && (long)g.nx * g.ny <= s->direct_cells && nsg::direct_fits(g.nx, g.ny);
+        return s->k.direct_cells > 0 && (long)g.nx * g.ny <= s->k.direct_cells && nsg::direct_fits(g.nx, g.ny);
     };
     for (;;) {
         const MgLevel& F = s->lv.back();
@@ -3093,7 +3070,7 @@ int build_levels(ns_solver* s, const std::vector<double>& hx0, const std::vector
     s->mg_coarse_lds = !s->mg_direct && (s->nranks == 1 || last.repl) && s->lv.size() > 1 &&
                        nsg::coarse_vcycle_bytes(gc) <= lds_cap;
     if (s->mg_direct) CHK(direct_setup(s, last));
-    if (s->verbose && s->rank == 0) {
+    if (s->k.verbose && s->rank == 0) {
         for (size_t l = 0; l < s->lv.size(); l++)
             fprintf(stderr, "nsgpu mg level %zu: %d x %d%s, rows/rank >= %d, %s\n", l, s->lv[l].g.nx, s->lv[l].g.ny,
                     s->lv[l].repl ? " (replicated)" : "", s->lv[l].minrows,
@@ -3256,7 +3233,7 @@ int consistent_rhs(ns_solver* s) {
 
 // whether the direct solve about to run (inside a step) checks its residual (pois_solve_fps)
 bool fps_checks_next(const ns_solver* s) {
-    return s->fps_strict || (s->fps_check > 0 && s->fps_solves % s->fps_check == 0);
+    return s->fps_strict || (s->k.fps_check > 0 && s->fps_solves % s->k.fps_check == 0);
 }
 
 // the (sum, sum^2) partials of rhs_phi -> the sums and the null-space shift (one rank: one launch)
@@ -3286,7 +3263,7 @@ int divergence_fps(ns_solver* s) {
     }
     double* b = fps_checks_next(s) ? s->arr[NS_ARR_RPHI] : nullptr;
     auto launch = [&](int phase) {
-        return nsg::launch_fps_div(s->g, s->c, s->dt, s->arr[NS_ARR_U], s->arr[NS_ARR_V], b, s->arr[NS_ARR_TMP],
+        return nsg::launch_fps_div(s->k, s->g, s->c, s->dt, s->arr[NS_ARR_U], s->arr[NS_ARR_V], b, s->arr[NS_ARR_TMP],
                                    s->part, phase, s->fps_tw, s->fps_wk, s->st, s->fa.outE);
     };
     const HaloReq r[2] = {{&s->g, s->arr[NS_ARR_U], 1}, {&s->g, s->arr[NS_ARR_V], 1}};
@@ -3323,7 +3300,7 @@ int divergence(ns_solver* s) {
     s->fps_pre = false;
     const HaloReq r[2] = {{&s->g, s->arr[NS_ARR_U], 1}, {&s->g, s->arr[NS_ARR_V], 1}};
     auto launch = [&]() {
-        return nsg::launch_div(s->g, s->c, s->dt, s->arr[NS_ARR_U], s->arr[NS_ARR_V], s->arr[NS_ARR_RPHI], s->part,
+        return nsg::launch_div(s->k, s->g, s->c, s->dt, s->arr[NS_ARR_U], s->arr[NS_ARR_V], s->arr[NS_ARR_RPHI], s->part,
                                s->st);
     };
     // (r5, deep ghost rows: the residual pass computed u*, v*'s ghost row -- no exchange)
@@ -3374,7 +3351,7 @@ int rhs(ns_solver* s, bool defer_norm = false) {
         int lo = 0;
         const nsg::Geo gk = deep_geo(s, e, &lo);
         nb = overlapped(s, r, s->cu_ext >= e ? 3 : 5, [&]() {
-            return nsg::launch_rhs(gk, s->c, s->dt, s->re, shp(s->arr[NS_ARR_U], lo, ld), shp(s->arr[NS_ARR_V], lo, ld),
+            return nsg::launch_rhs(s->k, gk, s->c, s->dt, s->re, shp(s->arr[NS_ARR_U], lo, ld), shp(s->arr[NS_ARR_V], lo, ld),
                                    shp(s->arr[NS_ARR_PHI], lo, ld), shp(s->arr[NS_ARR_CU], lo, ld),
                                    shp(s->arr[NS_ARR_CV], lo, ld), shp(s->arr[NS_ARR_RU], lo, ld),
                                    shp(s->arr[NS_ARR_RV], lo, ld), s->part, s->st, e + 2);
@@ -3385,7 +3362,7 @@ int rhs(ns_solver* s, bool defer_norm = false) {
         // (r6) the previous step's CorrectVelocities folded in: U, V hold u*, v*, PHI phi^n; the corrected u, v go to
         // the ping-pong partners (swapped below) and their min / max -- the previous step's monitor -- to S_MM
         double* mm = s->part + 4 * (size_t)nsg::max_partials(s->g);
-        nb = nsg::launch_rhs(s->g, s->c, s->dt, s->re, s->arr[NS_ARR_U], s->arr[NS_ARR_V], s->arr[NS_ARR_PHI],
+        nb = nsg::launch_rhs(s->k, s->g, s->c, s->dt, s->re, s->arr[NS_ARR_U], s->arr[NS_ARR_V], s->arr[NS_ARR_PHI],
                              s->arr[NS_ARR_CU], s->arr[NS_ARR_CV], s->arr[NS_ARR_RU], s->arr[NS_ARR_RV], s->part, s->st,
                              2, s->arr[NS_ARR_TMPU], s->arr[NS_ARR_TMPV], mm);
         if (nb < 0) { set_err("K1 with the deferred correction: launch refused"); return NS_EHIP; }
@@ -3402,7 +3379,7 @@ int rhs(ns_solver* s, bool defer_norm = false) {
     } else {
         const HaloReq r[3] = {{&s->g, s->arr[NS_ARR_U], 2}, {&s->g, s->arr[NS_ARR_V], 2}, {&s->g, s->arr[NS_ARR_PHI], 1}};
         nb = overlapped(s, r, 3, [&]() {
-            return nsg::launch_rhs(s->g, s->c, s->dt, s->re, s->arr[NS_ARR_U], s->arr[NS_ARR_V], s->arr[NS_ARR_PHI],
+            return nsg::launch_rhs(s->k, s->g, s->c, s->dt, s->re, s->arr[NS_ARR_U], s->arr[NS_ARR_V], s->arr[NS_ARR_PHI],
                                    s->arr[NS_ARR_CU], s->arr[NS_ARR_CV], s->arr[NS_ARR_RU], s->arr[NS_ARR_RV], s->part,
                                    s->st);
         });
@@ -3432,7 +3409,7 @@ int correct_launch(ns_solver* s, double* part2) {
     // finished solve leaves free (a speculative K5 whose check fails is re-run after the last cycle,
     // with that solve's cycle count: the guess is formed again)
     const ExtrapPlan p = extrap_plan(s, s->cur_cycles);
-    const bool guess = s->in_step && s->k5_guess && p.branch >= 1 && p.branch <= 3 && nsg::correct_streams(s->g);
+    const bool guess = s->in_step && s->k.k5_guess && p.branch >= 1 && p.branch <= 3 && nsg::correct_streams(s->k, s->g);
     s->guess_ready = 0;
     // (r5, deep slabs: the direct solve wrote phi's ghost rows -- no exchange)
     const bool have = s->deep && s->phi_ext && s->in_step;
@@ -3443,17 +3420,17 @@ int correct_launch(ns_solver* s, double* part2) {
     }
     const int nb = have ? [&]() {
         if (guess)
-            return nsg::launch_correct_guess(s->g, s->c, s->dt, s->arr[NS_ARR_U], s->arr[NS_ARR_V], s->arr[NS_ARR_TMPU],
+            return nsg::launch_correct_guess(s->k, s->g, s->c, s->dt, s->arr[NS_ARR_U], s->arr[NS_ARR_V], s->arr[NS_ARR_TMPU],
                                              s->arr[NS_ARR_TMPV], s->arr[NS_ARR_PHI], part2, p.h[0], p.h[1], p.h[2], p.c,
                                              s->arr[NS_ARR_TMP], s->st);
-        return nsg::launch_correct(s->g, s->c, s->dt, s->arr[NS_ARR_U], s->arr[NS_ARR_V], s->arr[NS_ARR_TMPU],
+        return nsg::launch_correct(s->k, s->g, s->c, s->dt, s->arr[NS_ARR_U], s->arr[NS_ARR_V], s->arr[NS_ARR_TMPU],
                                    s->arr[NS_ARR_TMPV], s->arr[NS_ARR_PHI], part2, s->st);
     }() : overlapped(s, r, 1, [&]() {
         if (guess)
-            return nsg::launch_correct_guess(s->g, s->c, s->dt, s->arr[NS_ARR_U], s->arr[NS_ARR_V], s->arr[NS_ARR_TMPU],
+            return nsg::launch_correct_guess(s->k, s->g, s->c, s->dt, s->arr[NS_ARR_U], s->arr[NS_ARR_V], s->arr[NS_ARR_TMPU],
                                              s->arr[NS_ARR_TMPV], s->arr[NS_ARR_PHI], part2, p.h[0], p.h[1], p.h[2], p.c,
                                              s->arr[NS_ARR_TMP], s->st);
-        return nsg::launch_correct(s->g, s->c, s->dt, s->arr[NS_ARR_U], s->arr[NS_ARR_V], s->arr[NS_ARR_TMPU],
+        return nsg::launch_correct(s->k, s->g, s->c, s->dt, s->arr[NS_ARR_U], s->arr[NS_ARR_V], s->arr[NS_ARR_TMPU],
                                    s->arr[NS_ARR_TMPV], s->arr[NS_ARR_PHI], part2, s->st);
     });
     if (t5 && nb >= 0) {
@@ -3502,6 +3479,639 @@ int check_arr(ns_solver* s, int which) {
     return 0;
 }
 
+// ---- ns_create, phase by phase: check the arguments, build the host geometry, choose the paths (every decision,
+// no HIP call), create the device resources (every hipMalloc), join the communicator
+
+// NSGPU_RCCL_LOOPBACK applies: one rank, or several with neither an ncclUniqueId nor a host transport (a virtual slab)
+bool want_loopback(const nsg::Knobs& k, const ns_params* p) {
+    const bool has_ht = p->host_transport && p->host_transport->exchange && p->host_transport->allreduce;
+    return k.loopback && (p->nranks == 1 || (!p->nccl_id && !has_ht));
+}
+
+// phase 1: everything that can be refused from the arguments alone
+int check_args(const ns_grid_desc* gd, const ns_params* p, const nsg::Knobs& k) {
+    if (gd->cell_id && !gd->face_edge) { set_err("a cell_id mask needs face_edge (the cells' boundary edges, Grid.h:33)"); return NS_EINVAL; }
+    if (gd->nx < 2 || gd->ny < 2) { set_err("one-cell-thick geometry is not supported (FluidSolver.cpp:470-477)"); return NS_EINVAL; }
+    if (!gd->hx || !gd->hy) { set_err("hx/hy missing"); return NS_EINVAL; }
+    if (!(p->dt > 0)) { set_err("Time step should be positive"); return NS_EINVAL; }
+    if (!(p->re > 0)) { set_err("Reynolds number should be positive"); return NS_EINVAL; }
+    if (p->nranks < 1 || p->rank < 0 || p->rank >= p->nranks) { set_err("bad rank/nranks"); return NS_EINVAL; }
+    const bool has_ht = p->host_transport && p->host_transport->exchange && p->host_transport->allreduce;
+    if (p->nranks > 1 && !p->nccl_id && !has_ht && !k.loopback) {
+        set_err("nranks > 1 needs an ncclUniqueId or a host transport");
+        return NS_EINVAL;
+    }
+    if (p->poisson != NS_POISSON_RBSOR && p->poisson != NS_POISSON_JACOBI && p->poisson != NS_POISSON_MG) {
+        set_err("unknown Poisson solver %d (NS_POISSON_MG 0, NS_POISSON_JACOBI 1, NS_POISSON_RBSOR 3; ABI %d)",
+                p->poisson, NSGPU_ABI_VERSION);
+        return NS_EINVAL;
+    }
+    for (int i = 0; i < gd->nx; i++)
+        if (!(gd->hx[i] > 0)) { set_err("hx[%d] = %g is not positive", i, gd->hx[i]); return NS_EINVAL; }
+    for (int j = 0; j < gd->ny; j++)
+        if (!(gd->hy[j] > 0)) { set_err("hy[%d] = %g is not positive", j, gd->hy[j]); return NS_EINVAL; }
+    return 0;
+}
+
+// phase 2's host vectors, uploaded in phase 4 (masked domains only; empty on a rectangle)
+struct HostGeo {
+    std::vector<nsg::EdgeDev> etab;   // the polygon's edges; [MAX_EDGES]: interior faces
+    std::vector<int32_t> fch;         // the topology plane: this slab's rows and HALO ghost rows on each side
+    std::vector<int32_t> mband;       // (li0, j0) of the mt tiles holding a wall-band cell (one rank)
+    std::vector<int32_t> ecell;       // plane offsets of the slab's domain cells that are not FC_DEEP
+};
+
+// ConstructGhostStencils (FluidSolver.cpp:84-103) of one edge
+int edge_dev(const ns_grid_desc* gd, const ns_params* p, int e, nsg::EdgeDev* D) {
+    const ns_edge& E = gd->edges[e];
+    *D = nsg::EdgeDev{0, E.nx, E.ny, 0.0, 0.0};
+    if (E.type == NS_BC_INLET_UNI) {
+        if (E.nx == 0) D->c1 = 2 * E.info; else D->c0 = 2 * E.info;
+    } else if (E.type == NS_BC_WALL) {
+        if (E.nx != 0) D->c1 = 2 * E.info; else D->c0 = 2 * E.info;
+    } else if (E.type == NS_BC_NEUMANN) {
+        // outflow: velocity ghost q, phi ghost 2.5 phi_0 - 2 phi_1 + 0.5 phi_2 (:98-101);
+        // the Poisson solve becomes BiCGStab on the true matrix (pois_solve_any)
+        D->neu = 1;
+        if (!gd->cell_id && p->poisson != NS_POISSON_MG) {
+            set_err("NEUMANN outflow edges need the multigrid-preconditioned Krylov Poisson solve "
+                    "(NS_POISSON_MG): the RB-SOR / Jacobi sweeps cannot relax the outflow rows");
+            return NS_EINVAL;
+        }
+    } else {
+        set_err("edge %d: boundary condition type %d is not supported (INLET_PARABOLIC / PRESSURE / unset "
+                "have no ghost stencil in the reference)", e, E.type);
+        return NS_EINVAL;
+    }
+    return 0;
+}
+
+// a masked domain's topology plane and the global in-domain cell count
+int mask_topology(ns_solver* s, const ns_grid_desc* gd, HostGeo& H) {
+    const nsg::Geo& g = s->g;
+    const int nx = gd->nx, ny = gd->ny;
+    auto inside = [&](int i, int j) { return i >= 0 && i < nx && j >= 0 && j < ny && gd->cell_id[(size_t)i * ny + j] >= 0; };
+    long nin = 0;
+    for (size_t c = 0; c < (size_t)nx * ny; c++) nin += gd->cell_id[c] >= 0;
+    if (nin == 0) { set_err("the cell_id mask holds no cell"); return NS_EINVAL; }
+    s->ncells = (double)nin;
+    H.fch.assign((size_t)(g.nxl + 2 * nsg::HALO) * g.ld, 0);
+    const int di[4] = {-1, 1, 0, 0}, dj[4] = {0, 0, -1, 1};
+    for (int li = -nsg::HALO; li < g.nxl + nsg::HALO; li++) {
+        const int i = g.i0 + li;
+        if (i < 0 || i >= nx) continue;
+        for (int j = 0; j < ny; j++) {
+            if (!inside(i, j)) continue;
+            int code = nsg::FC_IN;
+            for (int k = 0; k < 4; k++) {
+                const int t = gd->face_edge[((size_t)i * ny + j) * 4 + k];
+                const bool nb = inside(i + di[k], j + dj[k]);
+                // Grid::inDomain and Cell::edges must agree (the reference mixes both tests)
+                if (nb == (t >= 0) || t >= gd->n_edges) {
+                    set_err("cell (%d,%d) face %d: edge tag %d disagrees with the domain mask", i, j, k, t);
+                    return NS_EINVAL;
+                }
+                code |= (nb ? nsg::FC_INT : t) << (5 * k);
+                if (!nb && H.etab[t].neu) {   // the outflow phi ghost's two inward cells
+                    const int a1 = i - H.etab[t].enx, b1 = j - H.etab[t].eny;
+                    if (!inside(a1, b1) || !inside(a1 - H.etab[t].enx, b1 - H.etab[t].eny)) {
+                        set_err("cell (%d,%d): a NEUMANN face needs two cells inward (FluidSolver.cpp:100)", i, j);
+                        return NS_EINVAL;
+                    }
+                }
+            }
+            if (inside(i - 1, j) && inside(i - 2, j) && inside(i + 1, j) && inside(i + 2, j) && inside(i, j - 1) &&
+                inside(i, j - 2) && inside(i, j + 1) && inside(i, j + 2))
+                code |= nsg::FC_DEEP;
+            H.fch[(size_t)(li + nsg::HALO) * g.ld + j] = code;
+        }
+    }
+    return 0;
+}
+
+// (r6) the masked domain's wall bands (one rank): FC_BAND on the cells within mbw of a boundary face along
+// their row or column (on a rectangle exactly the box bands of helm_band), and the mt kernel's tiles holding one
+void mask_bands(const nsg::Geo& g, int mbw, HostGeo& H) {
+    const int nx = g.nx, ny = g.ny, ldh = g.ld;
+    auto code_at = [&](int i, int j) -> int32_t& { return H.fch[(size_t)(i + nsg::HALO) * ldh + j]; };
+    auto bnd = [&](int i, int j) {   // a domain cell with a face that is not interior
+        const int32_t c = code_at(i, j);
+        if (!(c & nsg::FC_IN)) return false;
+        for (int k = 0; k < 4; k++)
+            if (nsg::fc_edge(c, k) != nsg::FC_INT) return true;
+        return false;
+    };
+    const int BIG = 1 << 29;
+    std::vector<int> dr((size_t)nx * ny, BIG);   // distance along the row / column to a boundary cell
+    for (int i = 0; i < nx; i++) {
+        int last = -BIG;
+        for (int j = 0; j < ny; j++) { if (bnd(i, j)) last = j; dr[(size_t)i * ny + j] = j - last; }
+        last = BIG;
+        for (int j = ny - 1; j >= 0; j--) {
+            if (bnd(i, j)) last = j;
+            dr[(size_t)i * ny + j] = std::min(dr[(size_t)i * ny + j], last - j);
+        }
+    }
+    for (int j = 0; j < ny; j++) {
+        int last = -BIG;
+        for (int i = 0; i < nx; i++) {
+            if (bnd(i, j)) last = i;
+            dr[(size_t)i * ny + j] = std::min(dr[(size_t)i * ny + j], i - last);
+        }
+        last = BIG;
+        for (int i = nx - 1; i >= 0; i--) {
+            if (bnd(i, j)) last = i;
+            dr[(size_t)i * ny + j] = std::min(dr[(size_t)i * ny + j], last - i);
+        }
+    }
+    const int nti = (nx + nsg::MT_TI - 1) / nsg::MT_TI, ntj = (ny + nsg::MT_TJ - 1) / nsg::MT_TJ;
+    std::vector<char> tb((size_t)nti * ntj, 0);
+    for (int i = 0; i < nx; i++)
+        for (int j = 0; j < ny; j++)
+            if ((code_at(i, j) & nsg::FC_IN) && dr[(size_t)i * ny + j] < mbw) {
+                code_at(i, j) |= nsg::FC_BAND;
+                tb[(size_t)(i / nsg::MT_TI) * ntj + j / nsg::MT_TJ] = 1;
+            }
+    for (int a = 0; a < nti; a++)
+        for (int b = 0; b < ntj; b++)
+            if (tb[(size_t)a * ntj + b]) { H.mband.push_back(a * nsg::MT_TI); H.mband.push_back(b * nsg::MT_TJ); }
+}
+
+// this slab's bounding-box cells -> compact ids (i outer, j inner: ids increase along the slab's rows)
+int mask_compact_ids(ns_solver* s, const ns_grid_desc* gd) {
+    const int32_t* c = gd->cell_id + (size_t)s->g.i0 * gd->ny;
+    const size_t n = (size_t)s->g.nxl * gd->ny;
+    s->cid.assign(c, c + n);
+    int64_t lo = -1, cnt = 0;
+    for (size_t k = 0; k < n; k++)
+        if (c[k] >= 0) {
+            if (lo < 0) lo = c[k];
+            cnt++;
+        }
+    s->cid0 = lo < 0 ? 0 : lo;
+    s->ncid = cnt;
+    for (size_t k = 0; k < n; k++) {
+        if (c[k] < 0) continue;
+        const int64_t r = c[k] - s->cid0;
+        if (r < 0 || r >= cnt) {
+            set_err("cell_id is not the compact i-outer / j-inner numbering of Grid.cpp:149-162 (id %d)", c[k]);
+            return NS_EINVAL;
+        }
+        s->cid[k] = (int32_t)r;
+    }
+    return 0;
+}
+
+// phase 2: the slab, the rectangle's sides from its edges or the masked domain's topology.  Host vectors only
+int host_geometry(ns_solver* s, const ns_grid_desc* gd, const ns_params* p, HostGeo& H) {
+    const bool masked = gd->cell_id != nullptr;
+    nsg::Geo& g = s->g;
+    g.nx = gd->nx;
+    g.ny = gd->ny;
+    g.ld = (gd->ny + 127) / 128 * 128;
+    int32_t i0, i1;
+    if (ns_slab_range(gd->nx, p->nranks, p->rank, &i0, &i1)) return NS_EINVAL;
+    g.i0 = i0;
+    g.nxl = i1 - i0;
+    s->rank = p->rank;
+    s->nranks = p->nranks;
+    s->ncells = (double)gd->nx * gd->ny;
+    // (the widest exchange outside the 3-sweep passes is 6 rows, fed from one neighbour; the overlapped
+    // passes want an interior beyond it)
+    constexpr int min_slab_rows = 10;
+    if (p->nranks > 1 && g.nxl < min_slab_rows) {
+        set_err("slab of %d rows is thinner than the %d-row halo exchange", g.nxl, min_slab_rows);
+        return NS_EINVAL;
+    }
+    if (!masked) {
+        // sides from edge normals (a rectangle: Grid.cpp:35-63 gives one edge per side)
+        const int snx[4] = {-1, 1, 0, 0}, sny[4] = {0, 0, -1, 1};
+        int side_edge[4] = {-1, -1, -1, -1};
+        for (int e = 0; e < gd->n_edges; e++) {
+            const ns_edge& E = gd->edges[e];
+            for (int k = 0; k < 4; k++)
+                if (E.nx == snx[k] && E.ny == sny[k]) {
+                    if (side_edge[k] >= 0) { set_err("side %d has more than one edge: not a rectangle (pass cell_id / face_edge)", k); return NS_EINVAL; }
+                    side_edge[k] = e;
+                }
+        }
+        for (int k = 0; k < 4; k++) {
+            if (side_edge[k] < 0) { set_err("side %d has no edge: not a rectangle", k); return NS_EINVAL; }
+            nsg::EdgeDev D;
+            if (int rc = edge_dev(gd, p, side_edge[k], &D)) return rc;
+            g.enx[k] = D.enx;
+            g.eny[k] = D.eny;
+            g.c0[k] = D.c0;
+            g.c1[k] = D.c1;
+            g.neu[k] = D.neu;
+            if (D.neu && (k < 2 ? gd->nx : gd->ny) < 3) {
+                set_err("a NEUMANN side needs >= 3 cells along its normal (its phi ghost reaches 2 inward)");
+                return NS_EINVAL;
+            }
+        }
+        return 0;
+    }
+    H.etab.assign(nsg::MAX_EDGES + 1, nsg::EdgeDev{0, 0, 0, 0.0, 0.0});
+    if (gd->n_edges > nsg::MAX_EDGES) { set_err("more than %d polygon edges", nsg::MAX_EDGES); return NS_EINVAL; }
+    for (int e = 0; e < gd->n_edges; e++)
+        if (int rc = edge_dev(gd, p, e, &H.etab[e])) return rc;
+    if (int rc = mask_topology(s, gd, H)) return rc;
+    if (g.nxl == gd->nx) {
+        const int nmin = std::min(g.nx, g.ny);
+        const int mbw = s->k.mask_band_w > 0 ? s->k.mask_band_w : nmin > 4096 ? 3 * nmin / 64 : std::max(32, nmin / 32);
+        mask_bands(g, mbw, H);
+    }
+    for (int li = 0; li < g.nxl; li++)
+        for (int j = 0; j < g.ny; j++) {
+            const int32_t code = H.fch[(size_t)(li + nsg::HALO) * g.ld + j];
+            if ((code & nsg::FC_IN) && !(code & nsg::FC_DEEP)) H.ecell.push_back(li * g.ld + j);
+        }
+    return mask_compact_ids(s, gd);
+}
+
+// ns_params with their defaults
+void take_params(ns_solver* s, const ns_grid_desc* gd, const ns_params* p) {
+    s->dt = p->dt;
+    s->re = p->re;
+    s->rtol = p->rtol > 0 ? p->rtol : 1e-8;
+    s->poisson = p->poisson;
+    s->max_iters = p->max_iters > 0 ? p->max_iters : 200000;
+    const int nmax = std::max(gd->nx, gd->ny);
+    const double pi = 3.14159265358979323846;
+    s->omega = p->omega > 0 ? p->omega
+                            : (p->poisson != NS_POISSON_JACOBI ? 2.0 / (1.0 + std::sin(pi / nmax)) : 0.9);
+    {
+        // Helmholtz SOR weight: (I - a L_V) has Jacobi spectral radius
+        // rho = 2a(1/hx^2 + 1/hy^2) / (1 + 2a(1/hx^2 + 1/hy^2) + ...) <= that ratio on the finest spacing;
+        // optimal SOR omega = 2 / (1 + sqrt(1 - rho^2))
+        const double a = p->dt / (2 * p->re);
+        const double hxm = *std::min_element(gd->hx, gd->hx + gd->nx), hym = *std::min_element(gd->hy, gd->hy + gd->ny);
+        const double t = 2 * a * (1 / (hxm * hxm) + 1 / (hym * hym));
+        const double rho = t / (1 + t);
+        s->omega_v = p->omega_v > 0 ? p->omega_v : 2.0 / (1.0 + std::sqrt(1.0 - rho * rho));
+    }
+    s->check_every = p->check_every;
+    if (p->check_every > 0) s->pois_batch0 = s->helm_batch0 = p->check_every;
+    s->helm_next = s->helm_batch0;
+    s->helm_adapt = p->check_every <= 0;
+    s->timing = p->timing;
+    s->device = p->device;
+    if (s->device < 0) {
+        const char* lr = getenv("LOCAL_RANK");
+        s->device = lr ? atoi(lr) : 0;
+    }
+    if (p->poisson == NS_POISSON_MG) {
+        if (p->mg_pre > 0) s->mg_pre = p->mg_pre;
+        if (p->mg_post > 0) s->mg_post = p->mg_post;
+        if (p->mg_omega > 0) s->mg_omega_s = p->mg_omega;
+        if (s->k.mg_omega_set) s->mg_omega_s = s->k.mg_omega;   // smoother over-relaxation (A/B)
+    }
+}
+
+// a polygon's only NEUMANN edge is exactly the bounding box's W (side 0) or E (side 1) column: every cell of the
+// column in the domain with that edge on its outer face, and the edge on no other cell face -- e.g. the
+// backward-facing step's outflow
+bool neumann_is_box_column(const ns_grid_desc* gd, int side) {
+    int en = -1, nne = 0;
+    for (int e = 0; e < gd->n_edges; e++)
+        if (gd->edges[e].type == NS_BC_NEUMANN) { en = e; nne++; }
+    if (nne != 1) return false;
+    const int i = side == 0 ? 0 : gd->nx - 1;
+    for (int j = 0; j < gd->ny; j++) {
+        const size_t c = (size_t)i * gd->ny + j;
+        if (gd->cell_id[c] < 0 || gd->face_edge[4 * c + side] != en) return false;
+    }
+    long faces = 0;
+    for (size_t c = 0; c < (size_t)gd->nx * gd->ny; c++)
+        for (int f = 0; f < 4; f++) faces += gd->face_edge[4 * c + f] == en;
+    return faces == gd->ny;
+}
+
+// phase 3: every path decision that follows from the grid, the parameters, the knobs and the slab ranges.  No HIP
+// or RCCL call.  What needs a device query or a set-up's result is finished where that is known: comm_cus in
+// create_streams, fps_defer after fps_setup, the RB-SOR fallback after build_levels (both in create_solvers)
+int choose_paths(ns_solver* s, const ns_grid_desc* gd, const ns_params* p) {
+    const nsg::Knobs& k = s->k;
+    const nsg::Geo& g = s->g;
+    const bool masked = gd->cell_id != nullptr;
+    const int nmin = std::min(g.nx, g.ny);
+
+    // the walls' boundary layers span a fixed fraction of the grid: 1/32 of the shorter side (128
+    // at 4096^2; 8192^2 with 128 needed 8.5 global sweeps per step, with 256: 4.5 -- 7173 -> 8057
+    // MLUPS), at least 32
+    s->band_w = std::max(32, nmin / 32);
+    // (r5) the Helmholtz operator loses diagonal dominance as the grid grows (alpha / h^2 = n / (16 Re) at
+    // dt = h / 8: Jacobi radius 0.51 at 4096^2, 0.67 at 8192^2), so the band needs more sweeps there:
+    // 8192^2 with 6 sweeps in 256-wide bands took 4.5 global sweeps per step (4.55 ms), with 9 in 384-wide
+    // bands 3.0 (4.47 ms; 9 in 256: 5.8, 6 in 384 / 512: 4.5; profiles/r05/bands_8192.log)
+    // (16384^2: 12 sweeps in 768-wide bands 3.0 global sweeps, 31.9 ms per step; 9 in 768: 5.0, 34.1 ms;
+    // profiles/r05/bands_16384.log)
+    if (nmin > 4096) {
+        s->band_sweeps = nmin > 8192 ? 12 : 9;
+        s->band_w = 3 * nmin / 64;
+    }
+    if (k.band_w > 0) s->band_w = k.band_w;
+    if (k.band_sweeps > 0) s->band_sweeps = k.band_sweeps;
+    // (triple stays true on every decomposition ns_create accepts: the scan that was to clear it for slabs thinner
+    // than 2 * HALO rows ran over nranks before it was set, i.e. never, and slabs of 10 .. 13 rows have taken the
+    // 3-sweep passes ever since)
+
+    // a stretched grid (Grid.cpp ratio > 0) with no outflow edge needs the consistent rhs
+    bool stretched = false, outflow = false;
+    for (int i = 1; i < gd->nx; i++) stretched |= std::fabs(gd->hx[i] - gd->hx[0]) > 1e-12 * gd->hx[0];
+    for (int j = 1; j < gd->ny; j++) stretched |= std::fabs(gd->hy[j] - gd->hy[0]) > 1e-12 * gd->hy[0];
+    for (int e = 0; e < gd->n_edges; e++) outflow |= gd->edges[e].type == NS_BC_NEUMANN;
+    s->consist = stretched && !outflow;
+    double a = 0.0, ia = 0.0;
+    for (int i = 0; i < gd->nx; i++)
+        for (int j = 0; j < gd->ny; j++)
+            if (!masked || gd->cell_id[(size_t)i * gd->ny + j] >= 0) {
+                a += gd->hx[i] * gd->hy[j];
+                ia += 1.0 / (gd->hx[i] * gd->hy[j]);
+            }
+    s->area = a;
+    s->inv_area = ia;
+
+    // the direct Poisson solve: a rectangle without an outflow side, uniform hy (the DCT's premise), ny a power
+    // of two.  (r6) hx may be stretched (Grid.cpp:87-92): Lx's per-row coefficients enter Thomas' recurrences
+    // as they are (ns_fps.hip piv_next), and consistent_rhs makes b - plain mean area-consistent first (mode
+    // 0's singular system along x); the fused K3 form (uniform face weights) and the pivot fixed points
+    // (uniform interior rows) stay off there
+    bool yuni = true, xuni = true;
+    for (int j = 1; j < gd->ny; j++) yuni &= gd->hy[j] == gd->hy[0];
+    for (int i = 1; i < gd->nx; i++) xuni &= gd->hx[i] == gd->hx[0];
+    s->c.yuni = yuni;
+    // (r5) or a rectangle whose only NEUMANN side is E, on one rank with nx even (the outflow row is
+    // the second row of the last row pair, the elimination of ns_fps.hip's piv_next): the channel
+    const int nneu = g.neu[0] + g.neu[1] + g.neu[2] + g.neu[3];   // (a masked domain: 0)
+    // (r6) on slabs too: the outflow row pair is the last rank's last local pair (its row count even, >= 4), the
+    // mode-0 shift reaches the other ranks by one scalar all-reduce (pois_solve_fps)
+    int32_t lq0 = 0, lq1 = gd->nx;
+    if (p->nranks > 1) ns_slab_range(gd->nx, p->nranks, p->nranks - 1, &lq0, &lq1);
+    const bool out_ok = nneu == 1 && g.neu[1] && gd->nx % 2 == 0 && gd->nx >= 4 && (lq1 - lq0) % 2 == 0 &&
+                        lq1 - lq0 >= 4 && k.fps_outflow && xuni;   // (the elimination: uniform hx)
+    // (r6) the transforms along y: the FFT (hy uniform, ny a power of two or of 2, 3, 5, 7) or the dense
+    // eigenvector transforms (hy stretched, Grid.cpp:87-92, or another ny <= 4096; walls / inlets only)
+    const bool fft = yuni && (nsg::fps_log2x(gd->ny) >= 0 || nsg::fps_gen_ok(gd->ny));
+    const bool dense = !fft && !outflow && gd->ny >= 2 && gd->ny <= (yuni ? 4096 : 8192) && k.fps_dense;
+    s->fps = p->poisson == NS_POISSON_MG && k.fps && !masked && (fft ? (!outflow || out_ok) : dense);
+    s->fps_dense = s->fps && !fft;
+    s->fa.outE = s->fps && outflow ? 1 : 0;
+    s->fps_passes = k.fps_passes == 3 && !s->fa.outE ? 3 : 2;
+    if (k.fps_fuse >= 0) s->fps_fuse = k.fps_fuse != 0;
+    // (r5) ny = 16384 (configs[4]): the two-half transforms have no fused K3 form -- K3, then the DCT; (r6) the
+    // one-row transform has (fps_fuse_ok)
+    if (!nsg::fps_fuse_ok(k, gd->ny, s->fa.outE)) s->fps_fuse = false;
+    s->fps_xuni = xuni;
+    if (!xuni || s->fps_dense) s->fps_fuse = false;   // (r6: K3's general face weights, then the transform)
+    // (r5) or a masked domain whose only NEUMANN edge is its box's whole E column: the box's direct solve with the
+    // channel's outflow elimination
+    const bool mask_oe = masked && outflow && gd->nx % 2 == 0 && gd->nx >= 4 && k.fps_outflow && k.cap_outflow &&
+                         neumann_is_box_column(gd, 1);
+    s->fps_pc = p->poisson == NS_POISSON_MG && k.fps && k.fps_pc && masked && (!outflow || mask_oe) && yuni && xuni &&
+                p->nranks == 1 && nsg::fps_log2(gd->ny) >= 0;
+    if (s->fps_pc && outflow) s->fa.outE = 1;
+    if (k.phi_extrap >= 0) s->phi_extrap = k.phi_extrap;
+    if (s->fps) s->phi_extrap = 0;   // (no initial guess: no history planes)
+    // (r6) the capacitance solve (cap_setup, unless NSGPU_CAP=0) is exact: BiCGStab takes one iteration from
+    // any start, so no phi extrapolation (its k_axpby pass, 87 us at 4096^2, and its four history planes)
+    if (s->fps_pc && k.cap) s->phi_extrap = 0;
+
+    if (s->poisson == NS_POISSON_MG) {
+        // one NEUMANN side, W or E (a grid row: one slab's, contiguous) of a rectangle, or a polygon whose only
+        // NEUMANN edge is its box's W or E column (the box hierarchy takes the same closure on that side): the
+        // line-solve preconditioner (NSGPU_OUTFLOW_PC=wall: the round-1 wall closure, A/B)
+        const bool line_pc = g.ny <= 4096 && !k.outflow_pc_wall;
+        if (!masked && nneu == 1 && (g.neu[0] || g.neu[1]) && line_pc) s->out_side = g.neu[0] ? 0 : 1;
+        for (int side = 0; side < 2 && masked && line_pc && s->out_side < 0; side++)
+            if (neumann_is_box_column(gd, side)) s->out_side = side;
+        s->krylov_mg = true;
+    }
+
+    s->loopback = want_loopback(k, p);
+    if (s->loopback && p->nranks > 1) {
+        if ((size_t)k.virtual_iters_len >= sizeof k.virtual_iters) {
+            set_err("NSGPU_VIRTUAL_ITERS: a list of %d characters, at most %zu fit", k.virtual_iters_len,
+                    sizeof k.virtual_iters - 1);
+            return NS_EINVAL;
+        }
+        for (const char* q = k.virtual_iters; *q;) {
+            int h = 0, c = 0, used = 0;
+            if (std::sscanf(q, "%d:%d%n", &h, &c, &used) != 2 || h < 2 || c < 0) {
+                set_err("NSGPU_VIRTUAL_ITERS: expected sweeps:cycles pairs (sweeps >= 2), got '%s'", q);
+                return NS_EINVAL;
+            }
+            s->replay.emplace_back(h, c);
+            q += used;
+            if (*q == ',') q++;
+        }
+        // (its own residuals would not converge the global problem: never solve to tolerance)
+        if (s->replay.empty()) {
+            set_err("a virtual slab (NSGPU_RCCL_LOOPBACK with nranks > 1) needs NSGPU_VIRTUAL_ITERS");
+            return NS_EINVAL;
+        }
+    }
+    if (comm_on(s)) s->overlap = k.overlap != 0;
+    // (r5) the scalar bus of multi-rank rectangles (bus())
+    s->bus = s->nranks > 1 && !masked && k.bus;
+    {
+        // (r5) deep ghost rows (ns_solver::deep): multi-rank rectangles on the direct solve with the wall bands and
+        // the residual 3-sweep pass, every rank's slab at least deep_e + 3 rows (one neighbour feeds the exchange)
+        // (E1 = 8 + 6 R: the residual pass's 7-row cone plus the one row of each neighbour it computes for K3)
+        const int R = std::max(1, s->band_sweeps / 3), E1 = 8 + 6 * R;
+        bool ok = p->nranks > 1 && !masked && s->fps && k.helm_band && k.sweep3 && k.sweep3_res && s->triple && k.deep;
+        for (int q = 0; q < p->nranks && ok; q++) {
+            int32_t a0, a1;
+            ns_slab_range(g.nx, p->nranks, q, &a0, &a1);
+            ok = a1 - a0 >= E1 + 3;
+        }
+        if (ok) {
+            s->deep = true;
+            s->deep_e = E1;
+            s->hp = E1 + nsg::HALO + 2;
+        }
+    }
+    // (r6) K5 deferred into the next async step's K1 (k_rhs_sc): one rank, a rectangle without NEUMANN sides (the
+    // streaming K5's domain), the direct solve (no phi-history guess formed by K5), hy uniform (K1's correction
+    // takes GradP's y face weights as 0.5), the streaming K1; NSGPU_K5_DEFER=0: K5 at every step's end (A/B)
+    s->k5_defer_ok = !comm_on(s) && !masked && s->fps && yuni && k.rhs == nsg::Knobs::RHS_STREAM && !k.tiled &&
+                     nsg::correct_streams(k, g) && k.k5_defer;
+    if (k.verbose)
+        fprintf(stderr, "nsgpu rank %d/%d: %d x %d, rows %d; direct solve %d (outflow %d, fused K3 %d), wall bands %d "
+                "(%d sweeps, %d wide), 3-sweep passes %d (residual %d, triple %d), deep ghost rows %d (%d)\n",
+                s->rank, s->nranks, g.nx, g.ny, g.nxl, (int)s->fps, s->fa.outE, (int)s->fps_fuse, (int)k.helm_band,
+                s->band_sweeps, s->band_w, (int)k.sweep3, (int)k.sweep3_res, (int)s->triple, (int)s->deep,
+                s->deep_e);
+    return 0;
+}
+
+// phase 4's allocations: `bytes` at *ptr, zeroed on s->st if `zero`; the error text and code otherwise
+template <class T>
+int dev_alloc(ns_solver* s, T** ptr, size_t bytes, bool zero, const char* what) {
+    if (hipMalloc(ptr, bytes) != hipSuccess) { set_err("hipMalloc of %zu bytes (%s) failed", bytes, what); return NS_ENOMEM; }
+    if (zero && hipMemsetAsync(*ptr, 0, bytes, s->st) != hipSuccess) { set_err("memset (%s) failed", what); return NS_EHIP; }
+    return 0;
+}
+// ... filled from the host vector v
+template <class T>
+int dev_upload(ns_solver* s, T** ptr, const std::vector<T>& v, const char* what) {
+    CHK(dev_alloc(s, ptr, v.size() * sizeof(T), false, what));
+    if (hipMemcpy(*ptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) { set_err("%s upload failed", what); return NS_EHIP; }
+    return 0;
+}
+
+// the device, the compute stream and (multi-rank / loopback) the comm stream with its events
+int create_streams(ns_solver* s) {
+    const int dev = s->device;
+    if (hipSetDevice(dev) != hipSuccess) { set_err("hipSetDevice(%d) failed", dev); return NS_EHIP; }
+    // multi-rank, opt-in (NSGPU_COMM_CUS=n): the compute stream leaves n CUs to the comm stream,
+    // whose RCCL kernels then run beside the interior strips of an overlapped pass instead of
+    // queueing until the strips' resident round drains.  Off by default: the masked compute
+    // kernels lost what the exchanges gained (virtual-slab projections, profiles/r03)
+    int cus = 0;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    // (a single rank without the loopback has no comm traffic: no masks, every CU computes)
+    if (comm_on(s) && s->k.comm_cus > 0 && s->k.comm_cus < cus && cus <= 1024 && cus % 8 == 0) {
+        // the reserved CUs spread evenly over the 8 XCDs: workgroups are dispatched round-robin
+        // over the XCDs, so an XCD short of CUs would be every launch's straggler (all 8 on one
+        // XCD made the strips ~40 % slower).  Bit 32 x + ((x + 8 j) % 32), j < comm_cus / 8: one
+        // CU of XCD x per j whether mask bits number the CUs XCD-major or XCD-interleaved
+        const int per = cus / 8;
+        s->comm_cus = std::max(8, s->k.comm_cus / 8 * 8);
+        std::vector<uint32_t> mc((cus + 31) / 32, 0u), mx((cus + 31) / 32, 0u);
+        std::vector<char> comm_cu(cus, 0);
+        for (int x = 0; x < 8; x++)
+            for (int j = 0; j < s->comm_cus / 8; j++) comm_cu[per * x + (x + 8 * j) % per] = 1;
+        for (int k = 0; k < cus; k++) (comm_cu[k] ? mx : mc)[k / 32] |= 1u << (k % 32);
+        if (hipExtStreamCreateWithCUMask(&s->st, (uint32_t)mc.size(), mc.data()) != hipSuccess ||
+            hipExtStreamCreateWithCUMask(&s->cst, (uint32_t)mx.size(), mx.data()) != hipSuccess) {
+            set_err("CU-masked stream create failed");
+            return NS_EHIP;
+        }
+        s->compute_cus = cus - s->comm_cus;
+    }
+    if (!s->st && hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking) != hipSuccess) { set_err("stream create failed"); return NS_EHIP; }
+    if (hipEventCreateWithFlags(&s->fev, hipEventDisableTiming) != hipSuccess) { set_err("event create failed"); return NS_EHIP; }
+    if (comm_on(s) &&
+        ((!s->cst && hipStreamCreateWithFlags(&s->cst, hipStreamNonBlocking) != hipSuccess) ||
+         hipEventCreateWithFlags(&s->xev[0], hipEventDisableTiming) != hipSuccess ||
+         hipEventCreateWithFlags(&s->xev[1], hipEventDisableTiming) != hipSuccess)) {
+        set_err("comm stream / event create failed");
+        return NS_EHIP;
+    }
+    return 0;
+}
+
+// the field planes, the phi history planes, and a masked domain's topology
+int create_fields(ns_solver* s, const HostGeo& H) {
+    const nsg::Geo& g = s->g;
+    s->plane = (size_t)(g.nxl + 2 * s->hp) * g.ld;
+    CHK(dev_alloc(s, &s->base, s->plane * NS_NUM_ARR * sizeof(double), true, "fields"));
+    for (int k = 0; k < NS_NUM_ARR; k++) s->arr[k] = s->base + k * s->plane + (size_t)s->hp * g.ld;
+    if (s->phi_extrap) {
+        const size_t np = (size_t)std::min(s->phi_extrap, 4);
+        CHK(dev_alloc(s, &s->phim_mem, np * s->plane * sizeof(double), true, "phi history"));
+        s->phim = s->phim_mem + (size_t)s->hp * g.ld;
+        if (np >= 2) s->phim2 = s->phim + s->plane;
+        if (np >= 3) s->phim3 = s->phim2 + s->plane;
+        if (np >= 4) s->phim4 = s->phim3 + s->plane;
+    }
+    if (H.fch.empty()) return 0;
+    // (the device edge table padded to 32 entries: k_helm_mt_mask reads the NEUMANN flags of all 31 tags at once)
+    std::vector<nsg::EdgeDev> etd(H.etab);
+    if (etd.size() < 32) etd.resize(32, nsg::EdgeDev{});
+    CHK(dev_upload(s, &s->fc_mem, H.fch, "topology"));
+    CHK(dev_upload(s, &s->et_mem, etd, "topology"));
+    s->g.fc = s->fc_mem + (size_t)nsg::HALO * g.ld;
+    s->g.et = s->et_mem;
+    if (!H.mband.empty()) {
+        CHK(dev_upload(s, &s->mband_tiles, H.mband, "topology"));
+        s->mband_n = (int)(H.mband.size() / 2);
+    }
+    if (!H.ecell.empty()) {
+        CHK(dev_upload(s, &s->ecell_mem, H.ecell, "topology"));
+        s->g.ecell = s->ecell_mem;
+        s->g.necell = (int)H.ecell.size();
+    }
+    return 0;
+}
+
+// the coefficient tables (ConstructLHS, FluidSolver.cpp:113-131; computed once) and what each chosen solver
+// needs: the direct solve's tables, the multigrid hierarchy, the Krylov planes, the capacitance matrix
+int create_solvers(ns_solver* s, const ns_grid_desc* gd, const ns_params* p) {
+    const nsg::Geo& g = s->g;
+    const bool masked = gd->cell_id != nullptr;
+    const std::vector<double> hx0(gd->hx, gd->hx + g.nx), hy0(gd->hy, gd->hy + g.ny);
+    const std::vector<double> h = coef_tables(hx0, hy0, g.neu);
+    CHK(dev_upload(s, &s->coef, h, "coef"));
+    const int yuni = s->c.yuni;   // (choose_paths)
+    s->c = coef_view(s->coef, g.nx, g.ny);
+    s->c.yuni = yuni;
+    if (s->fps || s->fps_pc) CHK(fps_setup(s, hy0, h.data(), h.data() + g.nx));
+    // (r6: the deferred mean not with an outflow side -- its mode 0 takes the projected shift, the mean never enters;
+    // m0e: fps_setup built the mode-0 tables)
+    s->fps_defer = s->bus && s->fps && s->fps_fuse && s->m0e && !s->fa.outE && s->k.fps_defer;
+    // a masked domain's Poisson preconditioner: one V-cycle of the BOUNDING BOX's wall-closure
+    // multigrid (a fictitious-domain preconditioner: the rhs is 0 outside the domain, the
+    // outside values of the result are ignored by the masked operator), unless preconditioned by the box's
+    // direct solve, fps_pc, which never runs a V-cycle: its Poisson BiCGStab takes fps_precond, its Helmholtz
+    // BiCGStab the Jacobi preconditioner -- no hierarchy is allocated for it
+    if (s->poisson == NS_POISSON_MG) {
+        if (!s->fps_pc) CHK(build_levels(s, hx0, hy0));
+        if (p->mg_coarse_iters > 0) s->mg_coarse_iters = p->mg_coarse_iters;
+        if (s->lv.size() < 2 && !s->fps_pc) {
+            // nothing to coarsen: plain RB-SOR (O(n) sweeps per solve) -- say so when that is a
+            // real grid, not a toy
+            if ((long)g.nx * g.ny > 64L * 64L && s->rank == 0)
+                fprintf(stderr, "nsgpu: warning: the %d x %d grid cannot be coarsened (odd size%s): the multigrid "
+                        "Poisson solve falls back to red-black SOR sweeps\n", g.nx, g.ny,
+                        s->nranks > 1 ? " or slab edges" : "");
+            s->poisson = NS_POISSON_RBSOR;
+        }
+    }
+    if (masked || g.neu[0] || g.neu[1] || g.neu[2] || g.neu[3]) {
+        // BiCGStab planes (outflow rectangle: the preconditioner is the hierarchy above -- with a
+        // single level its coarse relaxation, 2n+10 SOR sweeps from zero; masked domain: Jacobi)
+        const size_t nk = sizeof(s->kv) / sizeof(s->kv[0]);
+        CHK(dev_alloc(s, &s->kv_mem, (nk * s->plane + g.ld) * sizeof(double), true, "Krylov planes"));
+        for (size_t k = 0; k < nk; k++) s->kv[k] = s->kv_mem + k * s->plane + (size_t)s->hp * g.ld;
+        s->lrow = s->kv_mem + nk * s->plane;
+        CHK(dev_alloc(s, &s->ksc, nsg::KS_NUM * sizeof(double), true, "Krylov scalars"));
+    }
+    if (s->fps_pc && s->kv[0])   // (r5) the masked domain's capacitance matrix
+        CHK(cap_setup(s, gd, h.data(), h.data() + g.nx, h.data() + 3 * g.nx, h.data() + 3 * g.nx + g.ny));
+    return 0;
+}
+
+// partials ([0, 4 np) for any kernel's, [4 np, 8 np) for a speculative K5's: correct_launch), scalars, the bus
+int create_scalars(ns_solver* s) {
+    const int np = nsg::max_partials(s->g);
+    CHK(dev_alloc(s, &s->part, (size_t)np * 8 * sizeof(double), false, "partials"));
+    CHK(dev_alloc(s, &s->scal, S_NUM * sizeof(double), true, "scalars"));
+    if (hipHostMalloc(&s->hs, S_NUM * sizeof(double), hipHostMallocDefault) != hipSuccess) { set_err("hipHostMalloc failed"); return NS_ENOMEM; }
+    if (s->bus) CHK(dev_alloc(s, &s->bus_mem, (size_t)BUS_NV * s->nranks * sizeof(double), true, "scalar bus"));
+    return 0;
+}
+
+// phase 5: the loopback's 1-rank communicator, the host transport, or this rank's place in the RCCL communicator
+int join_comm(ns_solver* s, const ns_params* p) {
+    if (s->loopback) {
+        ncclUniqueId id;
+        ncclResult_t r = ncclGetUniqueId(&id);
+        if (r == ncclSuccess) r = ncclCommInitRank(&s->comm, 1, id, 0);
+        if (r != ncclSuccess) { set_err("loopback ncclCommInitRank: %s", ncclGetErrorString(r)); return NS_ERCCL; }
+    } else if (s->nranks > 1 && p->host_transport && p->host_transport->exchange) {
+        s->ht = *p->host_transport;
+    } else if (s->nranks > 1) {
+        ncclUniqueId id;
+        std::memcpy(&id, p->nccl_id, sizeof id);
+        ncclResult_t r = ncclCommInitRank(&s->comm, s->nranks, id, s->rank);
+        if (r != ncclSuccess) { set_err("ncclCommInitRank: %s", ncclGetErrorString(r)); return NS_ERCCL; }
+    }
+    if (hipStreamSynchronize(s->st) != hipSuccess) { set_err("sync failed"); return NS_EHIP; }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3544,649 +4154,26 @@ int64_t ns_device_bytes(int32_t nxl, int32_t ny) {
 int ns_create(const ns_grid_desc* gd, const ns_params* p, ns_solver** out) {
     if (!gd || !p || !out) { set_err("null argument"); return NS_EINVAL; }
     *out = nullptr;
-    const bool masked = gd->cell_id != nullptr;
-    if (masked && !gd->face_edge) { set_err("a cell_id mask needs face_edge (the cells' boundary edges, Grid.h:33)"); return NS_EINVAL; }
-    if (gd->nx < 2 || gd->ny < 2) { set_err("one-cell-thick geometry is not supported (FluidSolver.cpp:470-477)"); return NS_EINVAL; }
-    if (!gd->hx || !gd->hy) { set_err("hx/hy missing"); return NS_EINVAL; }
-    if (!(p->dt > 0)) { set_err("Time step should be positive"); return NS_EINVAL; }
-    if (!(p->re > 0)) { set_err("Reynolds number should be positive"); return NS_EINVAL; }
-    if (p->nranks < 1 || p->rank < 0 || p->rank >= p->nranks) { set_err("bad rank/nranks"); return NS_EINVAL; }
-    const char* lbe = getenv("NSGPU_RCCL_LOOPBACK");
-    const bool has_ht = p->host_transport && p->host_transport->exchange && p->host_transport->allreduce;
-    const bool loopback = lbe && std::atoi(lbe) != 0 && (p->nranks == 1 || (!p->nccl_id && !has_ht));
-    if (p->nranks > 1 && !p->nccl_id && !has_ht && !loopback) {
-        set_err("nranks > 1 needs an ncclUniqueId or a host transport");
-        return NS_EINVAL;
-    }
-    if (p->poisson != NS_POISSON_RBSOR && p->poisson != NS_POISSON_JACOBI && p->poisson != NS_POISSON_MG) {
-        set_err("unknown Poisson solver %d (NS_POISSON_MG 0, NS_POISSON_JACOBI 1, NS_POISSON_RBSOR 3; ABI %d)",
-                p->poisson, NSGPU_ABI_VERSION);
-        return NS_EINVAL;
-    }
-
-    nsg::Geo g{};
-    g.nx = gd->nx;
-    g.ny = gd->ny;
-    g.ld = (gd->ny + 127) / 128 * 128;
-    int32_t i0, i1;
-    if (ns_slab_range(gd->nx, p->nranks, p->rank, &i0, &i1)) return NS_EINVAL;
-    g.i0 = i0;
-    g.nxl = i1 - i0;
-    // (the widest exchange outside the 3-sweep passes -- which need slabs of 2*HALO rows, `triple`
-    // -- is 6 rows, fed from one neighbour; the overlapped passes want an interior beyond it)
-    constexpr int min_slab_rows = 10;
-    if (p->nranks > 1 && g.nxl < min_slab_rows) {
-        set_err("slab of %d rows is thinner than the %d-row halo exchange", g.nxl, min_slab_rows);
-        return NS_EINVAL;
-    }
-    // ConstructGhostStencils (FluidSolver.cpp:84-103) of one edge
-    auto edge_dev = [&](int e, nsg::EdgeDev* D) -> int {
-        const ns_edge& E = gd->edges[e];
-        *D = nsg::EdgeDev{0, E.nx, E.ny, 0.0, 0.0};
-        if (E.type == NS_BC_INLET_UNI) {
-            if (E.nx == 0) D->c1 = 2 * E.info; else D->c0 = 2 * E.info;
-        } else if (E.type == NS_BC_WALL) {
-            if (E.nx != 0) D->c1 = 2 * E.info; else D->c0 = 2 * E.info;
-        } else if (E.type == NS_BC_NEUMANN) {
-            // outflow: velocity ghost q, phi ghost 2.5 phi_0 - 2 phi_1 + 0.5 phi_2 (:98-101);
-            // the Poisson solve becomes BiCGStab on the true matrix (pois_solve_any)
-            D->neu = 1;
-            if (!masked && p->poisson != NS_POISSON_MG) {
-                set_err("NEUMANN outflow edges need the multigrid-preconditioned Krylov Poisson solve "
-                        "(NS_POISSON_MG): the RB-SOR / Jacobi sweeps cannot relax the outflow rows");
-                return NS_EINVAL;
-            }
-        } else {
-            set_err("edge %d: boundary condition type %d is not supported (INLET_PARABOLIC / PRESSURE / unset "
-                    "have no ghost stencil in the reference)", e, E.type);
-            return NS_EINVAL;
-        }
-        return 0;
-    };
-    std::vector<nsg::EdgeDev> etab(nsg::MAX_EDGES + 1, nsg::EdgeDev{0, 0, 0, 0.0, 0.0});  // [31]: interior faces
-    if (masked) {
-        if (gd->n_edges > nsg::MAX_EDGES) { set_err("more than %d polygon edges", nsg::MAX_EDGES); return NS_EINVAL; }
-        for (int e = 0; e < gd->n_edges; e++)
-            if (int rc = edge_dev(e, &etab[e])) return rc;
-    } else {
-        // sides from edge normals (a rectangle: Grid.cpp:35-63 gives one edge per side)
-        const int snx[4] = {-1, 1, 0, 0}, sny[4] = {0, 0, -1, 1};
-        int side_edge[4] = {-1, -1, -1, -1};
-        for (int e = 0; e < gd->n_edges; e++) {
-            const ns_edge& E = gd->edges[e];
-            for (int k = 0; k < 4; k++)
-                if (E.nx == snx[k] && E.ny == sny[k]) {
-                    if (side_edge[k] >= 0) { set_err("side %d has more than one edge: not a rectangle (pass cell_id / face_edge)", k); return NS_EINVAL; }
-                    side_edge[k] = e;
-                }
-        }
-        for (int k = 0; k < 4; k++) {
-            if (side_edge[k] < 0) { set_err("side %d has no edge: not a rectangle", k); return NS_EINVAL; }
-            nsg::EdgeDev D;
-            if (int rc = edge_dev(side_edge[k], &D)) return rc;
-            g.enx[k] = D.enx;
-            g.eny[k] = D.eny;
-            g.c0[k] = D.c0;
-            g.c1[k] = D.c1;
-            g.neu[k] = D.neu;
-            if (D.neu && (k < 2 ? gd->nx : gd->ny) < 3) {
-                set_err("a NEUMANN side needs >= 3 cells along its normal (its phi ghost reaches 2 inward)");
-                return NS_EINVAL;
-            }
-        }
-    }
-
-    // masked domain: the topology plane (this slab's rows and HALO ghost rows on each side)
-    // and the global in-domain cell count
-    std::vector<int32_t> fch;
-    long nin = (long)gd->nx * gd->ny;
-    if (masked) {
-        const int nx = gd->nx, ny = gd->ny;
-        auto inside = [&](int i, int j) { return i >= 0 && i < nx && j >= 0 && j < ny && gd->cell_id[(size_t)i * ny + j] >= 0; };
-        nin = 0;
-        for (size_t c = 0; c < (size_t)nx * ny; c++) nin += gd->cell_id[c] >= 0;
-        if (nin == 0) { set_err("the cell_id mask holds no cell"); return NS_EINVAL; }
-        fch.assign((size_t)(g.nxl + 2 * nsg::HALO) * g.ld, 0);
-        const int di[4] = {-1, 1, 0, 0}, dj[4] = {0, 0, -1, 1};
-        for (int li = -nsg::HALO; li < g.nxl + nsg::HALO; li++) {
-            const int i = g.i0 + li;
-            if (i < 0 || i >= nx) continue;
-            for (int j = 0; j < ny; j++) {
-                if (!inside(i, j)) continue;
-                int code = nsg::FC_IN;
-                for (int k = 0; k < 4; k++) {
-                    const int t = gd->face_edge[((size_t)i * ny + j) * 4 + k];
-                    const bool nb = inside(i + di[k], j + dj[k]);
-                    // Grid::inDomain and Cell::edges must agree (the reference mixes both tests)
-                    if (nb == (t >= 0) || t >= gd->n_edges) {
-                        set_err("cell (%d,%d) face %d: edge tag %d disagrees with the domain mask", i, j, k, t);
-                        return NS_EINVAL;
-                    }
-                    code |= (nb ? nsg::FC_INT : t) << (5 * k);
-                    if (!nb && etab[t].neu) {   // the outflow phi ghost's two inward cells
-                        const int a1 = i - etab[t].enx, b1 = j - etab[t].eny;
-                        if (!inside(a1, b1) || !inside(a1 - etab[t].enx, b1 - etab[t].eny)) {
-                            set_err("cell (%d,%d): a NEUMANN face needs two cells inward (FluidSolver.cpp:100)", i, j);
-                            return NS_EINVAL;
-                        }
-                    }
-                }
-                if (inside(i - 1, j) && inside(i - 2, j) && inside(i + 1, j) && inside(i + 2, j) && inside(i, j - 1) &&
-                    inside(i, j - 2) && inside(i, j + 1) && inside(i, j + 2))
-                    code |= nsg::FC_DEEP;
-                fch[(size_t)(li + nsg::HALO) * g.ld + j] = code;
-            }
-        }
-    }
-
-    // (r6) the masked domain's wall bands (one rank): FC_BAND on the cells within mbw of a boundary face along
-    // their row or column (on a rectangle exactly the box bands of helm_band), and the mt kernel's tiles holding one
-    std::vector<int32_t> mband;
-    if (masked && g.nxl == gd->nx) {
-        const int nx = gd->nx, ny = gd->ny, ldh = g.ld;
-        int mbw = std::min(nx, ny) > 4096 ? 3 * std::min(nx, ny) / 64 : std::max(32, std::min(nx, ny) / 32);
-        if (const char* e = getenv("NSGPU_MASK_BAND_W")) mbw = std::max(1, std::atoi(e));   // (A/B)
-        auto code_at = [&](int i, int j) -> int32_t& { return fch[(size_t)(i + nsg::HALO) * ldh + j]; };
-        auto bnd = [&](int i, int j) {   // a domain cell with a face that is not interior
-            const int32_t c = code_at(i, j);
-            if (!(c & nsg::FC_IN)) return false;
-            for (int k = 0; k < 4; k++)
-                if (nsg::fc_edge(c, k) != nsg::FC_INT) return true;
-            return false;
-        };
-        const int BIG = 1 << 29;
-        std::vector<int> dr((size_t)nx * ny, BIG);   // distance along the row / column to a boundary cell
-        for (int i = 0; i < nx; i++) {
-            int last = -BIG;
-            for (int j = 0; j < ny; j++) { if (bnd(i, j)) last = j; dr[(size_t)i * ny + j] = j - last; }
-            last = BIG;
-            for (int j = ny - 1; j >= 0; j--) {
-                if (bnd(i, j)) last = j;
-                dr[(size_t)i * ny + j] = std::min(dr[(size_t)i * ny + j], last - j);
-            }
-        }
-        for (int j = 0; j < ny; j++) {
-            int last = -BIG;
-            for (int i = 0; i < nx; i++) {
-                if (bnd(i, j)) last = i;
-                dr[(size_t)i * ny + j] = std::min(dr[(size_t)i * ny + j], i - last);
-            }
-            last = BIG;
-            for (int i = nx - 1; i >= 0; i--) {
-                if (bnd(i, j)) last = i;
-                dr[(size_t)i * ny + j] = std::min(dr[(size_t)i * ny + j], last - i);
-            }
-        }
-        const int nti = (nx + nsg::MT_TI - 1) / nsg::MT_TI, ntj = (ny + nsg::MT_TJ - 1) / nsg::MT_TJ;
-        std::vector<char> tb((size_t)nti * ntj, 0);
-        for (int i = 0; i < nx; i++)
-            for (int j = 0; j < ny; j++)
-                if ((code_at(i, j) & nsg::FC_IN) && dr[(size_t)i * ny + j] < mbw) {
-                    code_at(i, j) |= nsg::FC_BAND;
-                    tb[(size_t)(i / nsg::MT_TI) * ntj + j / nsg::MT_TJ] = 1;
-                }
-        for (int a = 0; a < nti; a++)
-            for (int b = 0; b < ntj; b++)
-                if (tb[(size_t)a * ntj + b]) { mband.push_back(a * nsg::MT_TI); mband.push_back(b * nsg::MT_TJ); }
-    }
-
+    const nsg::Knobs k = nsg::Knobs::from_env();
+    if (int rc = check_args(gd, p, k)) return rc;               // 1: the arguments
     ns_solver* s = new ns_solver();
-    s->g = g;
-    if (masked) {
-        // compact ids of this slab (i outer, j inner: ids increase along the slab's rows)
-        const int32_t* c = gd->cell_id + (size_t)g.i0 * gd->ny;
-        const size_t n = (size_t)g.nxl * gd->ny;
-        s->cid.assign(c, c + n);
-        int64_t lo = -1, cnt = 0;
-        for (size_t k = 0; k < n; k++)
-            if (c[k] >= 0) {
-                if (lo < 0) lo = c[k];
-                cnt++;
-            }
-        s->cid0 = lo < 0 ? 0 : lo;
-        s->ncid = cnt;
-        for (size_t k = 0; k < n; k++) {
-            if (c[k] < 0) continue;
-            const int64_t r = c[k] - s->cid0;
-            if (r < 0 || r >= cnt) {
-                set_err("cell_id is not the compact i-outer / j-inner numbering of Grid.cpp:149-162 (id %d)", c[k]);
-                delete s;
-                return NS_EINVAL;
-            }
-            s->cid[k] = (int32_t)r;
-        }
+    s->k = k;
+    HostGeo H;
+    int rc = host_geometry(s, gd, p, H);                        // 2: host geometry
+    if (!rc) {
+        take_params(s, gd, p);
+        rc = choose_paths(s, gd, p);                            // 3: the paths
     }
-    s->dt = p->dt;
-    s->re = p->re;
-    s->rtol = p->rtol > 0 ? p->rtol : 1e-8;
-    s->poisson = p->poisson;
-    s->max_iters = p->max_iters > 0 ? p->max_iters : 200000;
-    const int nmax = std::max(gd->nx, gd->ny);
-    const double pi = 3.14159265358979323846;
-    s->omega = p->omega > 0 ? p->omega
-                            : (p->poisson != NS_POISSON_JACOBI ? 2.0 / (1.0 + std::sin(pi / nmax)) : 0.9);
-    {
-        // Helmholtz SOR weight: (I - a L_V) has Jacobi spectral radius
-        // rho = 2a(1/hx^2 + 1/hy^2) / (1 + 2a(1/hx^2 + 1/hy^2) + ...) <= that ratio on the finest spacing;
-        // optimal SOR omega = 2 / (1 + sqrt(1 - rho^2))
-        const double a = p->dt / (2 * p->re);
-        const double hxm = *std::min_element(gd->hx, gd->hx + gd->nx), hym = *std::min_element(gd->hy, gd->hy + gd->ny);
-        const double t = 2 * a * (1 / (hxm * hxm) + 1 / (hym * hym));
-        const double rho = t / (1 + t);
-        s->omega_v = p->omega_v > 0 ? p->omega_v : 2.0 / (1.0 + std::sqrt(1.0 - rho * rho));
+    if (rc) {   // (nothing on the device yet)
+        delete s;
+        return rc;
     }
-    s->check_every = p->check_every;
-    if (p->check_every > 0) s->pois_batch0 = s->helm_batch0 = p->check_every;
-    s->helm_next = s->helm_batch0;
-    s->helm_adapt = p->check_every <= 0;
-    s->timing = p->timing;
-    if (const char* e = getenv("NSGPU_SWEEP")) s->tiled = std::strcmp(e, "tiled") == 0;
-    if (const char* e = getenv("NSGPU_SWEEP3")) s->sweep3 = std::atoi(e) != 0;   // A/B: pairs only
-    if (const char* e = getenv("NSGPU_HELM_BAND")) s->helm_band = std::atoi(e) != 0;   // A/B: no wall bands
-    // the walls' boundary layers span a fixed fraction of the grid: 1/32 of the shorter side (128
-    // at 4096^2; 8192^2 with 128 needed 8.5 global sweeps per step, with 256: 4.5 -- 7173 -> 8057
-    // MLUPS), at least 32
-    s->band_w = std::max(32, std::min(s->g.nx, s->g.ny) / 32);
-    // (r5) the Helmholtz operator loses diagonal dominance as the grid grows (alpha / h^2 = n / (16 Re) at
-    // dt = h / 8: Jacobi radius 0.51 at 4096^2, 0.67 at 8192^2), so the band needs more sweeps there:
-    // 8192^2 with 6 sweeps in 256-wide bands took 4.5 global sweeps per step (4.55 ms), with 9 in 384-wide
-    // bands 3.0 (4.47 ms; 9 in 256: 5.8, 6 in 384 / 512: 4.5; profiles/r05/bands_8192.log)
-    // (16384^2: 12 sweeps in 768-wide bands 3.0 global sweeps, 31.9 ms per step; 9 in 768: 5.0, 34.1 ms;
-    // profiles/r05/bands_16384.log)
-    if (std::min(s->g.nx, s->g.ny) > 4096) {
-        s->band_sweeps = std::min(s->g.nx, s->g.ny) > 8192 ? 12 : 9;
-        s->band_w = 3 * std::min(s->g.nx, s->g.ny) / 64;
+    nsg::set_strip_rows(k.strip_rows);
+    if ((rc = create_streams(s)) || (rc = create_fields(s, H)) || (rc = create_solvers(s, gd, p)) ||   // 4: the device
+        (rc = create_scalars(s)) || (rc = join_comm(s, p))) {                                         // 5: the communicator
+        ns_destroy(s);
+        return rc;
     }
-    if (const char* e = getenv("NSGPU_BAND_W")) s->band_w = std::max(1, std::atoi(e));   // A/B: band width
-    if (const char* e = getenv("NSGPU_BAND_SWEEPS")) s->band_sweeps = std::max(3, std::atoi(e) / 3 * 3);
-    if (const char* e = getenv("NSGPU_BAND6")) s->band6 = std::atoi(e) != 0;
-    if (const char* e = getenv("NSGPU_SWEEP3_RES")) s->sweep3_res = std::atoi(e) != 0;   // A/B: batches end on pairs
-    if (const char* e = getenv("NSGPU_HELM_UV")) s->helm_uv = std::atoi(e);
-    // the 3-sweep pass reads HALO ghost rows, which one neighbour feeds only from slabs of
-    // >= 2*HALO rows; thinner slabs (the thinnest of all ranks: a global decision) take the
-    // same sweeps as a single sweep + pairs
-    for (int q = 0; q < s->nranks && s->nranks > 1; q++) {
-        int32_t a0, a1;
-        ns_slab_range(s->g.nx, s->nranks, q, &a0, &a1);
-        if (a1 - a0 < 2 * nsg::HALO) s->triple = false;
-    }
-    if (const char* e = getenv("NSGPU_FUSED_RESTRICT")) s->fuse_restrict = std::atoi(e) != 0;
-    if (const char* e = getenv("NSGPU_FUSED_PROLONG")) s->fuse_prolong = std::atoi(e) != 0;
-    if (const char* e = getenv("NSGPU_TILE_SMALL")) s->tile_small = std::atoi(e) != 0;
-    if (const char* e = getenv("NSGPU_EXT_TIMING")) s->ext_timing = std::atoi(e) != 0;
-    if (const char* e = getenv("NSGPU_PHI_EXTRAP")) s->phi_extrap = std::max(0, std::min(4, std::atoi(e)));
-    if (const char* e = getenv("NSGPU_MG_PREDICT")) s->mg_predict = std::atoi(e) != 0;
-    if (const char* e = getenv("NSGPU_SPECULATE")) s->speculate = std::atoi(e) != 0;
-    if (const char* e = getenv("NSGPU_K5_GUESS")) s->k5_guess = std::atoi(e) != 0;
-    if (const char* e = getenv("NSGPU_FUSE4")) s->fuse4 = std::atoi(e) != 0;
-    if (const char* e = getenv("NSGPU_GIN")) s->gin = std::atoi(e) != 0;
-    if (const char* e = getenv("NSGPU_VERBOSE")) s->verbose = std::atoi(e) != 0;
-    if (const char* e = getenv("NSGPU_MASK_HELM")) s->mask_rb = std::strcmp(e, "krylov") != 0;
-    if (const char* e = getenv("NSGPU_MASK_RBT")) s->mask_rbt = std::atoi(e) != 0;
-    if (const char* e = getenv("NSGPU_MASK_MT")) s->mask_mt = std::atoi(e) != 0;
-    if (const char* e = getenv("NSGPU_MASK_BAND")) s->mask_band = std::max(0, std::atoi(e) / 6 * 6);
-    if (const char* e = getenv("NSGPU_PAIR_MIN_CELLS")) s->pair_min_cells = std::atol(e);
-    if (const char* e = getenv("NSGPU_DIRECT_CELLS")) s->direct_cells = std::max(0L, std::atol(e));
-    {
-        const char* e = getenv("NSGPU_STRIP_ROWS");  // tuning override; unset = adaptive
-        nsg::set_strip_rows(e ? atoi(e) : 0);
-    }
-    s->rank = p->rank;
-    s->nranks = p->nranks;
-    s->ncells = (double)nin;
-    {
-        // a stretched grid (Grid.cpp ratio > 0) with no outflow edge needs the consistent rhs
-        bool stretched = false, outflow = false;
-        for (int i = 1; i < gd->nx; i++) stretched |= std::fabs(gd->hx[i] - gd->hx[0]) > 1e-12 * gd->hx[0];
-        for (int j = 1; j < gd->ny; j++) stretched |= std::fabs(gd->hy[j] - gd->hy[0]) > 1e-12 * gd->hy[0];
-        for (int e = 0; e < gd->n_edges; e++) outflow |= gd->edges[e].type == NS_BC_NEUMANN;
-        s->consist = stretched && !outflow;
-        double a = 0.0, ia = 0.0;
-        for (int i = 0; i < gd->nx; i++)
-            for (int j = 0; j < gd->ny; j++)
-                if (!masked || gd->cell_id[(size_t)i * gd->ny + j] >= 0) {
-                    a += gd->hx[i] * gd->hy[j];
-                    ia += 1.0 / (gd->hx[i] * gd->hy[j]);
-                }
-        s->area = a;
-        s->inv_area = ia;
-        // the direct Poisson solve: a rectangle without an outflow side, uniform hy (the DCT's premise), ny a power
-        // of two.  (r6) hx may be stretched (Grid.cpp:87-92): Lx's per-row coefficients enter Thomas' recurrences
-        // as they are (ns_fps.hip piv_next), and consistent_rhs makes b - plain mean area-consistent first (mode
-        // 0's singular system along x); the fused K3 form (uniform face weights) and the pivot fixed points
-        // (uniform interior rows) stay off there
-        bool yuni = true, xuni = true;
-        for (int j = 1; j < gd->ny; j++) yuni &= gd->hy[j] == gd->hy[0];
-        for (int i = 1; i < gd->nx; i++) xuni &= gd->hx[i] == gd->hx[0];
-        const char* fe = getenv("NSGPU_FPS");
-        // (r5) or a rectangle whose only NEUMANN side is E, on one rank with nx even (the outflow row is
-        // the second row of the last row pair, the elimination of ns_fps.hip's piv_next): the channel
-        const int nneu_r = masked ? 0 : g.neu[0] + g.neu[1] + g.neu[2] + g.neu[3];
-        const char* foe = getenv("NSGPU_FPS_OUTFLOW");
-        // (r6) on slabs too: the outflow row pair is the last rank's last local pair (its row count even, >= 4), the
-        // mode-0 shift reaches the other ranks by one scalar all-reduce (pois_solve_fps)
-        int32_t lq0 = 0, lq1 = gd->nx;
-        if (p->nranks > 1) ns_slab_range(gd->nx, p->nranks, p->nranks - 1, &lq0, &lq1);
-        const bool out_ok = nneu_r == 1 && g.neu[1] && gd->nx % 2 == 0 && gd->nx >= 4 && (lq1 - lq0) % 2 == 0 &&
-                            lq1 - lq0 >= 4 && !(foe && std::atoi(foe) == 0) && xuni;   // (the elimination: uniform hx)
-        // (r6) the transforms along y: the FFT (hy uniform, ny a power of two or of 2, 3, 5, 7) or the dense
-        // eigenvector transforms (hy stretched, Grid.cpp:87-92, or another ny <= 4096; walls / inlets only)
-        const bool fft = yuni && (nsg::fps_log2x(gd->ny) >= 0 || nsg::fps_gen_ok(gd->ny));
-        const char* fdn = getenv("NSGPU_FPS_DENSE");
-        const bool dense = !fft && !outflow && gd->ny >= 2 && gd->ny <= (yuni ? 4096 : 8192) &&
-                           !(fdn && std::atoi(fdn) == 0);
-        s->fps = p->poisson == NS_POISSON_MG && !(fe && std::atoi(fe) == 0) && !masked &&
-                 (fft ? (!outflow || out_ok) : dense);
-        s->fps_dense = s->fps && !fft;
-        s->fa.outE = s->fps && outflow ? 1 : 0;
-        if (const char* e = getenv("NSGPU_FPS_CHECK")) s->fps_check = std::max(0, std::atoi(e));
-        if (const char* e = getenv("NSGPU_FPS_PASSES")) s->fps_passes = std::atoi(e) == 3 && !s->fa.outE ? 3 : 2;
-        if (const char* e = getenv("NSGPU_FPS_FUSE")) s->fps_fuse = std::atoi(e) != 0;
-        // (r5) ny = 16384 (configs[4]): the two-half transforms have no fused K3 form -- K3, then the DCT; (r6) the
-        // one-row transform has (fps_fuse_ok)
-        if (!nsg::fps_fuse_ok(gd->ny, s->fa.outE)) s->fps_fuse = false;
-        s->fps_xuni = xuni;
-        if (!xuni || s->fps_dense) s->fps_fuse = false;   // (r6: K3's general face weights, then the transform)
-        if (s->fps) s->phi_extrap = 0;   // (no initial guess: no history planes)
-        const char* fpc = getenv("NSGPU_FPS_PC");
-        // (r5) or a masked domain whose only NEUMANN edge is its box's whole E column (the backward-facing step):
-        // the box's direct solve with the channel's outflow elimination
-        bool mask_oe = false;
-        if (masked && outflow && gd->nx % 2 == 0 && gd->nx >= 4 && !(foe && std::atoi(foe) == 0) &&
-            !(getenv("NSGPU_CAP_OUTFLOW") && std::atoi(getenv("NSGPU_CAP_OUTFLOW")) == 0)) {
-            int en = -1, nne = 0;
-            for (int e = 0; e < gd->n_edges; e++)
-                if (gd->edges[e].type == NS_BC_NEUMANN) { en = e; nne++; }
-            bool whole = nne == 1;
-            for (int j = 0; j < gd->ny && whole; j++) {
-                const size_t c = (size_t)(gd->nx - 1) * gd->ny + j;
-                whole = gd->cell_id[c] >= 0 && gd->face_edge[4 * c + 1] == en;
-            }
-            long faces = 0;
-            for (size_t c = 0; c < (size_t)gd->nx * gd->ny && whole; c++)
-                for (int f = 0; f < 4; f++) faces += gd->face_edge[4 * c + f] == en;
-            mask_oe = whole && faces == gd->ny;
-        }
-        s->fps_pc = p->poisson == NS_POISSON_MG && !(fe && std::atoi(fe) == 0) && !(fpc && std::atoi(fpc) == 0) &&
-                    masked && (!outflow || mask_oe) && yuni && xuni && p->nranks == 1 && nsg::fps_log2(gd->ny) >= 0;
-        if (s->fps_pc && outflow) s->fa.outE = 1;
-        // (r6) the capacitance solve (cap_setup, unless NSGPU_CAP=0) is exact: BiCGStab takes one iteration from
-        // any start, so no phi extrapolation (its k_axpby pass, 87 us at 4096^2, and its four history planes)
-        const char* cpe = getenv("NSGPU_CAP");
-        if (s->fps_pc && !(cpe && std::atoi(cpe) == 0)) s->phi_extrap = 0;
-    }
-
-    auto fail = [&](int rc) { ns_destroy(s); return rc; };
-    int dev = p->device;
-    if (dev < 0) {
-        const char* lr = getenv("LOCAL_RANK");
-        dev = lr ? atoi(lr) : 0;
-    }
-    s->device = dev;
-    if (hipSetDevice(dev) != hipSuccess) { set_err("hipSetDevice(%d) failed", dev); return fail(NS_EHIP); }
-    {
-        // multi-rank, opt-in (NSGPU_COMM_CUS=n): the compute stream leaves n CUs to the comm stream,
-        // whose RCCL kernels then run beside the interior strips of an overlapped pass instead of
-        // queueing until the strips' resident round drains.  Off by default: the masked compute
-        // kernels lost what the exchanges gained (virtual-slab projections, profiles/r03)
-        int cus = 0;
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        const bool comm = p->nranks > 1 || loopback;
-        s->comm_cus = 0;
-        if (const char* e = getenv("NSGPU_COMM_CUS")) s->comm_cus = std::max(0, std::atoi(e));
-        // (a single rank without the loopback has no comm traffic: no masks, every CU computes)
-        if (comm && s->comm_cus > 0 && s->comm_cus < cus && cus <= 1024 && cus % 8 == 0) {
-            // the reserved CUs spread evenly over the 8 XCDs: workgroups are dispatched round-robin
-            // over the XCDs, so an XCD short of CUs would be every launch's straggler (all 8 on one
-            // XCD made the strips ~40 % slower).  Bit 32 x + ((x + 8 j) % 32), j < comm_cus / 8: one
-            // CU of XCD x per j whether mask bits number the CUs XCD-major or XCD-interleaved
-            const int per = cus / 8;
-            s->comm_cus = std::max(8, s->comm_cus / 8 * 8);
-            std::vector<uint32_t> mc((cus + 31) / 32, 0u), mx((cus + 31) / 32, 0u);
-            std::vector<char> comm_cu(cus, 0);
-            for (int x = 0; x < 8; x++)
-                for (int j = 0; j < s->comm_cus / 8; j++) comm_cu[per * x + (x + 8 * j) % per] = 1;
-            for (int k = 0; k < cus; k++) (comm_cu[k] ? mx : mc)[k / 32] |= 1u << (k % 32);
-            if (hipExtStreamCreateWithCUMask(&s->st, (uint32_t)mc.size(), mc.data()) != hipSuccess ||
-                hipExtStreamCreateWithCUMask(&s->cst, (uint32_t)mx.size(), mx.data()) != hipSuccess) {
-                set_err("CU-masked stream create failed");
-                return fail(NS_EHIP);
-            }
-            s->compute_cus = cus - s->comm_cus;
-        } else {
-            s->comm_cus = 0;
-        }
-    }
-    if (!s->st && hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking) != hipSuccess) { set_err("stream create failed"); return fail(NS_EHIP); }
-    if (hipEventCreateWithFlags(&s->fev, hipEventDisableTiming) != hipSuccess) { set_err("event create failed"); return fail(NS_EHIP); }
-    s->loopback = loopback;
-    if (loopback && p->nranks > 1) {
-        if (const char* e = getenv("NSGPU_VIRTUAL_ITERS")) {
-            for (const char* q = e; *q;) {
-                int h = 0, c = 0, used = 0;
-                if (std::sscanf(q, "%d:%d%n", &h, &c, &used) != 2 || h < 2 || c < 0) {
-                    set_err("NSGPU_VIRTUAL_ITERS: expected sweeps:cycles pairs (sweeps >= 2), got '%s'", q);
-                    return fail(NS_EINVAL);
-                }
-                s->replay.emplace_back(h, c);
-                q += used;
-                if (*q == ',') q++;
-            }
-        }
-        // (its own residuals would not converge the global problem: never solve to tolerance)
-        if (s->replay.empty()) {
-            set_err("a virtual slab (NSGPU_RCCL_LOOPBACK with nranks > 1) needs NSGPU_VIRTUAL_ITERS");
-            return fail(NS_EINVAL);
-        }
-    }
-    if (p->nranks > 1 || s->loopback) {
-        const char* ov = getenv("NSGPU_OVERLAP");
-        s->overlap = ov ? std::atoi(ov) != 0 : 1;
-        if ((!s->cst && hipStreamCreateWithFlags(&s->cst, hipStreamNonBlocking) != hipSuccess) ||
-            hipEventCreateWithFlags(&s->xev[0], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&s->xev[1], hipEventDisableTiming) != hipSuccess) {
-            set_err("comm stream / event create failed");
-            return fail(NS_EHIP);
-        }
-    }
-
-    {
-        // (r5) deep ghost rows (ns_solver::deep): multi-rank rectangles on the direct solve with the wall bands and
-        // the residual 3-sweep pass, every rank's slab at least deep_e + 3 rows (one neighbour feeds the exchange)
-        const char* de = getenv("NSGPU_DEEP");
-        // (E1 = 8 + 6 R: the residual pass's 7-row cone plus the one row of each neighbour it computes for K3)
-        const int R = std::max(1, s->band_sweeps / 3), E1 = 8 + 6 * R;
-        bool ok = p->nranks > 1 && !masked && s->fps && s->helm_band && s->sweep3 && s->sweep3_res && s->triple &&
-                  !(de && std::atoi(de) == 0);
-        for (int q = 0; q < p->nranks && ok; q++) {
-            int32_t a0, a1;
-            ns_slab_range(g.nx, p->nranks, q, &a0, &a1);
-            ok = a1 - a0 >= E1 + 3;
-        }
-        if (ok) {
-            s->deep = true;
-            s->deep_e = E1;
-            s->hp = E1 + nsg::HALO + 2;
-        }
-        if (s->verbose)
-            fprintf(stderr, "nsgpu rank %d/%d: %d x %d, rows %d; direct solve %d (outflow %d, fused K3 %d), wall bands %d "
-                    "(%d sweeps, %d wide), 3-sweep passes %d (residual %d, triple %d), deep ghost rows %d (%d)\n",
-                    s->rank, s->nranks, g.nx, g.ny, g.nxl, (int)s->fps, s->fa.outE, (int)s->fps_fuse, (int)s->helm_band,
-                    s->band_sweeps, s->band_w, (int)s->sweep3, (int)s->sweep3_res, (int)s->triple, (int)s->deep,
-                    s->deep_e);
-    }
-    s->plane = (size_t)(g.nxl + 2 * s->hp) * g.ld;
-    if (hipMalloc(&s->base, s->plane * NS_NUM_ARR * sizeof(double)) != hipSuccess) {
-        set_err("hipMalloc of %zu bytes failed", s->plane * NS_NUM_ARR * sizeof(double));
-        return fail(NS_ENOMEM);
-    }
-    if (hipMemsetAsync(s->base, 0, s->plane * NS_NUM_ARR * sizeof(double), s->st) != hipSuccess) { set_err("memset failed"); return fail(NS_EHIP); }
-    for (int k = 0; k < NS_NUM_ARR; k++) s->arr[k] = s->base + k * s->plane + (size_t)s->hp * g.ld;
-    if (s->phi_extrap) {
-        const size_t np = (size_t)std::min(s->phi_extrap, 4);
-        if (hipMalloc(&s->phim_mem, np * s->plane * sizeof(double)) != hipSuccess) { set_err("hipMalloc phim failed"); return fail(NS_ENOMEM); }
-        if (hipMemsetAsync(s->phim_mem, 0, np * s->plane * sizeof(double), s->st) != hipSuccess) { set_err("memset failed"); return fail(NS_EHIP); }
-        s->phim = s->phim_mem + (size_t)s->hp * g.ld;
-        if (np >= 2) s->phim2 = s->phim + s->plane;
-        if (np >= 3) s->phim3 = s->phim2 + s->plane;
-        if (np >= 4) s->phim4 = s->phim3 + s->plane;
-    }
-
-    if (masked) {
-        // (the device edge table padded to 32 entries: k_helm_mt_mask reads the NEUMANN flags of all 31 tags at once)
-        std::vector<nsg::EdgeDev> etd(etab.begin(), etab.end());
-        if (etd.size() < 32) etd.resize(32, nsg::EdgeDev{});
-        if (hipMalloc(&s->fc_mem, fch.size() * sizeof(int32_t)) != hipSuccess ||
-            hipMalloc(&s->et_mem, etd.size() * sizeof(nsg::EdgeDev)) != hipSuccess) { set_err("hipMalloc topology failed"); return fail(NS_ENOMEM); }
-        if (hipMemcpy(s->fc_mem, fch.data(), fch.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(s->et_mem, etd.data(), etd.size() * sizeof(nsg::EdgeDev), hipMemcpyHostToDevice) != hipSuccess) { set_err("topology upload failed"); return fail(NS_EHIP); }
-        s->g.fc = s->fc_mem + (size_t)nsg::HALO * g.ld;
-        s->g.et = s->et_mem;
-        if (!mband.empty()) {
-            if (hipMalloc(&s->mband_tiles, mband.size() * sizeof(int32_t)) != hipSuccess) { set_err("hipMalloc topology failed"); return fail(NS_ENOMEM); }
-            if (hipMemcpy(s->mband_tiles, mband.data(), mband.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) { set_err("topology upload failed"); return fail(NS_EHIP); }
-            s->mband_n = (int)(mband.size() / 2);
-        }
-        std::vector<int32_t> ec;
-        for (int li = 0; li < g.nxl; li++)
-            for (int j = 0; j < g.ny; j++) {
-                const int32_t code = fch[(size_t)(li + nsg::HALO) * g.ld + j];
-                if ((code & nsg::FC_IN) && !(code & nsg::FC_DEEP)) ec.push_back(li * g.ld + j);
-            }
-        if (!ec.empty()) {
-            if (hipMalloc(&s->ecell_mem, ec.size() * sizeof(int32_t)) != hipSuccess) { set_err("hipMalloc topology failed"); return fail(NS_ENOMEM); }
-            if (hipMemcpy(s->ecell_mem, ec.data(), ec.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) { set_err("topology upload failed"); return fail(NS_EHIP); }
-            s->g.ecell = s->ecell_mem;
-            s->g.necell = (int)ec.size();
-        }
-    }
-
-    // coefficient tables (ConstructLHS, FluidSolver.cpp:113-131)
-    std::vector<double> hx0(gd->hx, gd->hx + g.nx), hy0(gd->hy, gd->hy + g.ny);
-    for (int i = 0; i < g.nx; i++)
-        if (!(hx0[i] > 0)) { set_err("hx[%d] = %g is not positive", i, hx0[i]); return fail(NS_EINVAL); }
-    for (int j = 0; j < g.ny; j++)
-        if (!(hy0[j] > 0)) { set_err("hy[%d] = %g is not positive", j, hy0[j]); return fail(NS_EINVAL); }
-    {
-        const std::vector<double> h = coef_tables(hx0, hy0, g.neu);
-        if (hipMalloc(&s->coef, h.size() * sizeof(double)) != hipSuccess) { set_err("hipMalloc coef failed"); return fail(NS_ENOMEM); }
-        if (hipMemcpy(s->coef, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) { set_err("coef upload failed"); return fail(NS_EHIP); }
-        s->c = coef_view(s->coef, g.nx, g.ny);
-        s->c.yuni = 1;
-        for (int j = 1; j < g.ny; j++) s->c.yuni &= hy0[j] == hy0[0];
-        if (s->fps || s->fps_pc)
-            if (int rc = fps_setup(s, hy0, h.data(), h.data() + g.nx)) return fail(rc);
-    }
-    // a masked domain's Poisson preconditioner: one V-cycle of the BOUNDING BOX's wall-closure
-    // multigrid (a fictitious-domain preconditioner: the rhs is 0 outside the domain, the
-    // outside values of the result are ignored by the masked operator), unless
-    if (s->poisson == NS_POISSON_MG) {
-        // one NEUMANN side, W or E (a grid row: one slab's, contiguous) of a rectangle: the
-        // line-solve preconditioner (NSGPU_OUTFLOW_PC=wall: the round-1 wall closure, A/B)
-        const int nneu = g.neu[0] + g.neu[1] + g.neu[2] + g.neu[3];
-        const char* ope = getenv("NSGPU_OUTFLOW_PC");
-        const bool line_pc = g.ny <= 4096 && !(ope && !std::strcmp(ope, "wall"));
-        if (!masked && nneu == 1 && (g.neu[0] || g.neu[1]) && line_pc) s->out_side = g.neu[0] ? 0 : 1;
-        if (masked && line_pc) {
-            // a polygon whose only NEUMANN edge is exactly the bounding box's W or E column (every
-            // cell of it in the domain -- e.g. the backward-facing step's outflow): the box
-            // hierarchy takes the same line closure on that side
-            int en = -1, nne = 0;
-            for (int e = 0; e < gd->n_edges; e++)
-                if (gd->edges[e].type == NS_BC_NEUMANN) { en = e; nne++; }
-            for (int k = 0; k < 2 && nne == 1 && s->out_side < 0; k++) {
-                const int i = k == 0 ? 0 : g.nx - 1;
-                bool whole = true;
-                for (int j = 0; j < g.ny && whole; j++) {
-                    const size_t c = (size_t)i * g.ny + j;
-                    whole = gd->cell_id[c] >= 0 && gd->face_edge[4 * c + k] == en;
-                }
-                long faces = 0;   // the edge must not reach any other cell face
-                for (size_t c = 0; c < (size_t)g.nx * g.ny && whole; c++)
-                    for (int f = 0; f < 4; f++) faces += gd->face_edge[4 * c + f] == en;
-                if (whole && faces == g.ny) s->out_side = k;
-            }
-        }
-        if (p->mg_pre > 0) s->mg_pre = p->mg_pre;
-        if (p->mg_omega > 0) s->mg_omega_s = p->mg_omega;
-        if (const char* e = getenv("NSGPU_MG_OMEGA")) s->mg_omega_s = std::atof(e);   // smoother over-relaxation (A/B)
-        if (p->mg_post > 0) s->mg_post = p->mg_post;
-        // (a masked domain preconditioned by the box's direct solve, fps_pc, never runs a V-cycle: its
-        // Poisson BiCGStab takes fps_precond, its Helmholtz BiCGStab the Jacobi preconditioner -- no
-        // hierarchy is allocated for it)
-        if (!s->fps_pc)
-            if (int rc = build_levels(s, hx0, hy0)) return fail(rc);
-        if (p->mg_coarse_iters > 0) s->mg_coarse_iters = p->mg_coarse_iters;
-        if (s->lv.size() < 2 && !s->fps_pc) {
-            // nothing to coarsen: plain RB-SOR (O(n) sweeps per solve) -- say so when that is a
-            // real grid, not a toy
-            if ((long)g.nx * g.ny > 64L * 64L && s->rank == 0)
-                fprintf(stderr, "nsgpu: warning: the %d x %d grid cannot be coarsened (odd size%s): the multigrid "
-                        "Poisson solve falls back to red-black SOR sweeps\n", g.nx, g.ny,
-                        s->nranks > 1 ? " or slab edges" : "");
-            s->poisson = NS_POISSON_RBSOR;
-        }
-        s->krylov_mg = true;
-    }
-    if (masked || g.neu[0] || g.neu[1] || g.neu[2] || g.neu[3]) {
-        // BiCGStab planes (outflow rectangle: the preconditioner is the hierarchy above -- with a
-        // single level its coarse relaxation, 2n+10 SOR sweeps from zero; masked domain: Jacobi)
-        const size_t nk = sizeof(s->kv) / sizeof(s->kv[0]);
-        const size_t kn = nk * s->plane + g.ld;
-        if (hipMalloc(&s->kv_mem, kn * sizeof(double)) != hipSuccess) { set_err("hipMalloc Krylov planes failed"); return fail(NS_ENOMEM); }
-        if (hipMemsetAsync(s->kv_mem, 0, kn * sizeof(double), s->st) != hipSuccess) { set_err("memset failed"); return fail(NS_EHIP); }
-        for (size_t k = 0; k < nk; k++) s->kv[k] = s->kv_mem + k * s->plane + (size_t)s->hp * g.ld;
-        s->lrow = s->kv_mem + nk * s->plane;
-        if (hipMalloc(&s->ksc, nsg::KS_NUM * sizeof(double)) != hipSuccess) { set_err("hipMalloc failed"); return fail(NS_ENOMEM); }
-        if (hipMemsetAsync(s->ksc, 0, nsg::KS_NUM * sizeof(double), s->st) != hipSuccess) { set_err("memset failed"); return fail(NS_EHIP); }
-    }
-    if (s->fps_pc && s->kv[0]) {   // (r5) the masked domain's capacitance matrix
-        const std::vector<double> h = coef_tables(hx0, hy0, g.neu);
-        if (int rc = cap_setup(s, gd, h.data(), h.data() + g.nx, h.data() + 3 * g.nx, h.data() + 3 * g.nx + g.ny))
-            return fail(rc);
-    }
-    const int np = nsg::max_partials(g);
-    // partials: [0, 4 np) for any kernel's, [4 np, 8 np) for a speculative K5's (correct_launch)
-    if (hipMalloc(&s->part, (size_t)np * 8 * sizeof(double)) != hipSuccess) { set_err("hipMalloc partials failed"); return fail(NS_ENOMEM); }
-    if (hipMalloc(&s->scal, S_NUM * sizeof(double)) != hipSuccess) { set_err("hipMalloc scalars failed"); return fail(NS_ENOMEM); }
-    if (hipMemsetAsync(s->scal, 0, S_NUM * sizeof(double), s->st) != hipSuccess) { set_err("memset failed"); return fail(NS_EHIP); }
-    if (hipHostMalloc(&s->hs, S_NUM * sizeof(double), hipHostMallocDefault) != hipSuccess) { set_err("hipHostMalloc failed"); return fail(NS_ENOMEM); }
-    // (r5) the scalar bus of multi-rank rectangles (bus())
-    {
-        const char* be = getenv("NSGPU_BUS");
-        s->bus = s->nranks > 1 && !masked && !(be && std::atoi(be) == 0);
-        if (s->bus && (hipMalloc(&s->bus_mem, (size_t)BUS_NV * s->nranks * sizeof(double)) != hipSuccess ||
-                       hipMemsetAsync(s->bus_mem, 0, (size_t)BUS_NV * s->nranks * sizeof(double), s->st) != hipSuccess)) {
-            set_err("hipMalloc of the scalar bus failed");
-            return fail(NS_ENOMEM);
-        }
-        const char* de = getenv("NSGPU_FPS_DEFER");
-        // (r6: not with an outflow side -- its mode 0 takes the projected shift, the mean never enters)
-    s->fps_defer = s->bus && s->fps && s->fps_fuse && s->m0e && !s->fa.outE && !(de && std::atoi(de) == 0);
-    {
-        // (r6) K5 deferred into the next async step's K1 (k_rhs_sc): one rank, a rectangle without NEUMANN sides (the
-        // streaming K5's domain), the direct solve (no phi-history guess formed by K5), hy uniform (K1's correction
-        // takes GradP's y face weights as 0.5); NSGPU_K5_DEFER=0: K5 at every step's end (A/B)
-        const char* kd = getenv("NSGPU_K5_DEFER");
-        s->k5_defer_ok = !comm_on(s) && !s->g.fc && s->fps && s->c.yuni && !getenv("NSGPU_RHS") && !s->tiled &&
-                         nsg::correct_streams(s->g) && !(kd && std::atoi(kd) == 0);
-    }
-    }
-
-    if (s->loopback) {
-        ncclUniqueId id;
-        ncclResult_t r = ncclGetUniqueId(&id);
-        if (r == ncclSuccess) r = ncclCommInitRank(&s->comm, 1, id, 0);
-        if (r != ncclSuccess) { set_err("loopback ncclCommInitRank: %s", ncclGetErrorString(r)); return fail(NS_ERCCL); }
-    } else if (s->nranks > 1 && p->host_transport && p->host_transport->exchange) {
-        s->ht = *p->host_transport;
-    } else if (s->nranks > 1) {
-        ncclUniqueId id;
-        std::memcpy(&id, p->nccl_id, sizeof id);
-        ncclResult_t r = ncclCommInitRank(&s->comm, s->nranks, id, s->rank);
-        if (r != ncclSuccess) { set_err("ncclCommInitRank: %s", ncclGetErrorString(r)); return fail(NS_ERCCL); }
-    }
-    if (hipStreamSynchronize(s->st) != hipSuccess) { set_err("sync failed"); return fail(NS_EHIP); }
     *out = s;
     return 0;
 }
@@ -4265,7 +4252,7 @@ static int step_body_(ns_solver* s, ns_stats& st) {
     // rhs ghost rows (a checked pair pass and the 3-sweep pass read ib-5): multi-rank passes take them with
     // their first overlapped exchange
     if (s->deep) {   // (r5: K1 computed the rhs deep into the neighbours' rows)
-    } else if (s->nranks > 1 && s->overlap && s->cst && !s->g.fc && !s->tiled) s->helm_b_pend = 1;
+    } else if (s->nranks > 1 && s->overlap && s->cst && !s->g.fc && !s->k.tiled) s->helm_b_pend = 1;
     else CHK(halo(s, {s->arr[NS_ARR_RU], s->arr[NS_ARR_RV]}, 6));
     s->hn = 0;
     // the Poisson initial guess (phi extrapolation) waits to hide the Helmholtz check's host sync
@@ -4543,7 +4530,7 @@ int ns_kernel(ns_solver* s, int which, int iters, double* out) {
         // (rest-1)/2 two-sweep passes, then single sweeps; the residual is of the last sweep's input
         int nb = 0;
         CHK(halo(s, {s->arr[NS_ARR_RU], s->arr[NS_ARR_RV]}, 6));
-        const int three = (s->sweep3 && s->nranks == 1 && !s->tiled && iters >= 4) ? 3 : 0;
+        const int three = (s->k.sweep3 && s->nranks == 1 && !s->k.tiled && iters >= 4) ? 3 : 0;
         if (three) helm_sweep3(s, alpha, 1), helm_sweep3(s, alpha, 2);
         const int pairs = iters - three > 0 ? (iters - three - 1) / 2 : 0;
         for (int k = 0; k < pairs; k++) {
@@ -4563,7 +4550,7 @@ int ns_kernel(ns_solver* s, int which, int iters, double* out) {
         return 0;
     }
     case NS_K_HELM_BAND: {
-        if (s->g.fc || s->tiled) { set_err("NS_K_HELM_BAND needs a rectangle and the streaming sweeps"); return NS_EINVAL; }
+        if (s->g.fc || s->k.tiled) { set_err("NS_K_HELM_BAND needs a rectangle and the streaming sweeps"); return NS_EINVAL; }
         CHK(halo(s, {s->arr[NS_ARR_RU], s->arr[NS_ARR_RV]}, 6));
         CHK(helm_band(s, alpha));
         CHK(fetch(s));
@@ -4582,10 +4569,10 @@ int ns_kernel(ns_solver* s, int which, int iters, double* out) {
         }
         int nb = 0;
         CHK(halo(s, {s->arr[NS_ARR_RPHI]}, 4));
-        const int pairs = (s->poisson != NS_POISSON_JACOBI && !s->tiled && iters > 0) ? (iters - 1) / 2 : 0;
+        const int pairs = (s->poisson != NS_POISSON_JACOBI && !s->k.tiled && iters > 0) ? (iters - 1) / 2 : 0;
         for (int k = 0; k < pairs; k++) {
             CHK(halo(s, {s->arr[NS_ARR_PHI]}, 4));
-            nsg::launch_pois_rbsor2(s->g, s->c, s->omega, s->arr[NS_ARR_PHI], s->arr[NS_ARR_TMP], s->arr[NS_ARR_RPHI],
+            nsg::launch_pois_rbsor2(s->k, s->g, s->c, s->omega, s->arr[NS_ARR_PHI], s->arr[NS_ARR_TMP], s->arr[NS_ARR_RPHI],
                                     s->scal + S_SHIFT, nullptr, s->st);
             std::swap(s->arr[NS_ARR_PHI], s->arr[NS_ARR_TMP]);
         }
@@ -4717,7 +4704,7 @@ int ns_time_poisson(ns_solver* s, int warmup, int iters, double* out) {
     nsg::set_compute_cus(s->compute_cus);
     CHK(ensure_events(s, 2 * (size_t)iters));
     // NSGPU_TIME_PAIRS=1: time the two-sweep (temporally blocked) pass instead of a single sweep
-    const bool pairs = getenv("NSGPU_TIME_PAIRS") && s->poisson != NS_POISSON_JACOBI;
+    const bool pairs = s->k.time_pairs && s->poisson != NS_POISSON_JACOBI;
     auto one = [&](double* part) -> int {
         if (!pairs) {
             CHK(halo(s, {s->arr[NS_ARR_PHI]}, 2));
@@ -4725,7 +4712,7 @@ int ns_time_poisson(ns_solver* s, int warmup, int iters, double* out) {
             return 0;
         }
         CHK(halo(s, {s->arr[NS_ARR_PHI]}, part ? 5 : 4));
-        nsg::launch_pois_rbsor2(s->g, s->c, s->omega, s->arr[NS_ARR_PHI], s->arr[NS_ARR_TMP], s->arr[NS_ARR_RPHI],
+        nsg::launch_pois_rbsor2(s->k, s->g, s->c, s->omega, s->arr[NS_ARR_PHI], s->arr[NS_ARR_TMP], s->arr[NS_ARR_RPHI],
                                 s->scal + S_SHIFT, part, s->st);
         std::swap(s->arr[NS_ARR_PHI], s->arr[NS_ARR_TMP]);
         return 0;

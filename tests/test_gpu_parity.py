@@ -959,3 +959,84 @@ def test_streaming_poisson_apply_matches_grid_kernel(gpu, monkeypatch, nx, ny, b
     assert float(rel(out["stream"][1], out["grid"][1])) <= 1e-8
     xp, _ = og.solve_poisson(b)
     assert float(rel(out["stream"][1], xp - xp.mean())) <= 1e-8
+
+
+def _live_rhs(gpu):
+    rng = np.random.default_rng(41)
+    ins = [rand(rng, 37 * 70) for _ in range(5)]
+
+    def run(gs):
+        for a, x in zip((gpu.NS_ARR_U, gpu.NS_ARR_V, gpu.NS_ARR_PHI, gpu.NS_ARR_CU, gpu.NS_ARR_CV), ins):
+            gs.set(a, x)
+        sums = gs.kernel(gpu.NS_K_RHS)
+        return [gs.get(a) for a in (gpu.NS_ARR_RU, gpu.NS_ARR_RV, gpu.NS_ARR_CU, gpu.NS_ARR_CV)] + [sums]
+    return (lambda: pair(gpu, 37, 70, 1e-3, 250.0)[1]), run
+
+
+def _live_cell(gpu):
+    rng = np.random.default_rng(42)
+    u, v, phi = (rand(rng, 37 * 70) for _ in range(3))
+
+    def run(gs):
+        gs.set(gpu.NS_ARR_U, u); gs.set(gpu.NS_ARR_V, v); gs.set(gpu.NS_ARR_PHI, phi)
+        sums = gs.kernel(gpu.NS_K_DIV)
+        rp = gs.get(gpu.NS_ARR_RPHI)
+        mm = gs.kernel(gpu.NS_K_CORRECT)
+        return [rp, sums, mm, gs.get(gpu.NS_ARR_U), gs.get(gpu.NS_ARR_V)]
+    return (lambda: pair(gpu, 37, 70, 1e-3, 100.0)[1]), run
+
+
+def _live_mask_cell(gpu):
+    from polygons import ALL
+
+    def box_cells(P):
+        return sum(s[2] for s in P["xspec"]) * sum(s[2] for s in P["yspec"])
+    P = min(ALL.values(), key=box_cells)   # (the smallest polygon: 24 x 20)
+    og = OGrid(P["vertices"], P["xspec"], P["yspec"], P["bc"])
+    rng = np.random.default_rng(43)
+    vals = {a: rng.uniform(-1, 1, og.N) for a in (gpu.NS_ARR_U, gpu.NS_ARR_V)}
+
+    def make():
+        return gpu.GpuSolver(gpu.polygon(P["vertices"], og.hx, og.hy, P["bc"]), 1.0 / 512, 100.0)
+
+    def run(gs):
+        m = gs.grid.mask.ravel()
+        for a, x in vals.items():
+            p = np.zeros(m.size)
+            p[m] = x
+            gs.set(a, p)
+        sums = gs.kernel(gpu.NS_K_DIV)
+        return [gs.get(gpu.NS_ARR_RPHI), sums]
+    return make, run
+
+
+def _live_fps_real(gpu):
+    nx, ny = 33, 16384   # (the smallest ny whose fused row transform has no pair fallback)
+
+    def run(gs):
+        mm = [[st[k] for k in ("umin", "umax", "vmin", "vmax", "it_u", "it_phi")] for st in (gs.step() for _ in range(2))]
+        return [np.array(mm)] + [np.asarray(x) for x in gs.fields()]
+    return (lambda: gpu.GpuSolver(gpu.rectangle(nx, ny, lx=nx / ny), 1.0 / (8 * ny), 1000.0, rtol=1e-10)), run
+
+
+@pytest.mark.parametrize("var,val,case", [("NSGPU_RHS", "global", _live_rhs), ("NSGPU_CELL", "grid", _live_cell),
+                                          ("NSGPU_MASK_CELL", "0", _live_mask_cell),
+                                          ("NSGPU_FPS_REAL", "0", _live_fps_real)])
+def test_live_solver_ignores_later_env(gpu, monkeypatch, var, val, case):
+    """A knob's value is a property of the solver, fixed at ns_create (ns_knobs.h): solver A is created with the
+    variable unset and runs its operation with the variable set; solver B is created and run with it unset
+    throughout.  The same launches, so the same outputs bit for bit.  (NSGPU_FPS_REAL at ny = 16384: the launch
+    used to follow the environment while the fused-K3 decision was create's, and the step failed.)"""
+    make, run = case(gpu)
+    monkeypatch.delenv(var, raising=False)
+    a = make()
+    monkeypatch.setenv(var, val)
+    out_a = run(a)
+    a.close()
+    monkeypatch.delenv(var)
+    b = make()
+    out_b = run(b)
+    b.close()
+    assert len(out_a) == len(out_b)
+    for x, y in zip(out_a, out_b):
+        np.testing.assert_array_equal(x, y)
