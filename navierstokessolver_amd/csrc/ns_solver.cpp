@@ -144,7 +144,6 @@ struct ns_solver {
     int helm_batch0 = 4, pois_batch0 = 8;
     int helm_next = 4;           // first Helmholtz batch of the next step (adaptive unless check_every)
     int helm_adapt = 1;
-    bool triple = true;          // 3-sweep passes allowed on this decomposition
     // the Helmholtz wall bands (k.helm_band): their width (cells from a wall: min(nx, ny) / 32) and RB-SOR sweeps (a
     // multiple of 3).  (r6) k.band6, 6 band sweeps as ONE k_helm_band6 launch + copy-back: half the band bytes, but
     // the launches are latency-bound, not HBM-bound -- 100 + 13 us against 2 x 48.5 (profiles/r06/ab/): off
@@ -683,7 +682,7 @@ int helm_sweeps(ns_solver* s, double alpha, int n, double* part_first, double* p
     int nb = 0;
     // one rank: u's passes, then v's -- or, with helm_uv, a batch of a single 3-sweep residual pass
     // per component as ONE two-field launch (each field's strips twice as long: one resident round)
-    const bool split = s->nranks == 1 && !(s->k.helm_uv && n == 3 && s->k.sweep3 && s->triple && s->k.sweep3_res &&
+    const bool split = s->nranks == 1 && !(s->k.helm_uv && n == 3 && s->k.sweep3 && s->k.sweep3_res &&
                                           !part_first && !s->k.tiled);
     for (int which : {split ? 1 : 3, split ? 2 : 0}) {
         if (!which) break;
@@ -699,7 +698,7 @@ int helm_sweeps(ns_solver* s, double alpha, int n, double* part_first, double* p
                 // (a batch may also end on a 3-sweep pass with the residual stage, 7-row cone:
                 // 5 = 3+2, 3 = 3, 6 = 3+3 -- slabs too, with 7 ghost rows)
                 const bool end3 = s->k.sweep3_res;
-                if (s->k.sweep3 && s->triple && (n - k >= 5 || (end3 && (n - k == 3 || n - k == 6)))) w = 3;
+                if (s->k.sweep3 && (n - k >= 5 || (end3 && (n - k == 3 || n - k == 6)))) w = 3;
                 else if (((n - k) & 1) && n - k >= 3) w = 1;
             }
             const bool last = k + w >= n;
@@ -3676,12 +3675,19 @@ int host_geometry(ns_solver* s, const ns_grid_desc* gd, const ns_params* p, Host
     s->rank = p->rank;
     s->nranks = p->nranks;
     s->ncells = (double)gd->nx * gd->ny;
-    // (the widest exchange outside the 3-sweep passes is 6 rows, fed from one neighbour; the overlapped
-    // passes want an interior beyond it)
+    // (the widest exchange is the residual 3-sweep pass's 7 rows = HALO, fed from one neighbour; a slab too thin
+    // for an overlapped pass to have an interior runs the pass whole after its exchange, plan_rows -- slabs of 10
+    // to 13 rows take the 3-sweep passes: test_thin_slabs_take_three_sweep_passes)
+    // (every rank's slab, not only this one's: a rank whose own slab is wide enough would otherwise go on to
+    // exchange ghost rows with a neighbour whose ns_create failed)
     constexpr int min_slab_rows = 10;
-    if (p->nranks > 1 && g.nxl < min_slab_rows) {
-        set_err("slab of %d rows is thinner than the %d-row halo exchange", g.nxl, min_slab_rows);
-        return NS_EINVAL;
+    for (int q = 0; q < p->nranks && p->nranks > 1; q++) {
+        int32_t a0, a1;
+        if (ns_slab_range(gd->nx, p->nranks, q, &a0, &a1)) return NS_EINVAL;
+        if (a1 - a0 < min_slab_rows) {
+            set_err("rank %d's slab of %d rows is thinner than the %d-row halo exchange", q, a1 - a0, min_slab_rows);
+            return NS_EINVAL;
+        }
     }
     if (!masked) {
         // sides from edge normals (a rectangle: Grid.cpp:35-63 gives one edge per side)
@@ -3812,9 +3818,6 @@ int choose_paths(ns_solver* s, const ns_grid_desc* gd, const ns_params* p) {
     }
     if (k.band_w > 0) s->band_w = k.band_w;
     if (k.band_sweeps > 0) s->band_sweeps = k.band_sweeps;
-    // (triple stays true on every decomposition ns_create accepts: the scan that was to clear it for slabs thinner
-    // than 2 * HALO rows ran over nranks before it was set, i.e. never, and slabs of 10 .. 13 rows have taken the
-    // 3-sweep passes ever since)
 
     // a stretched grid (Grid.cpp ratio > 0) with no outflow edge needs the consistent rhs
     bool stretched = false, outflow = false;
@@ -3919,7 +3922,7 @@ int choose_paths(ns_solver* s, const ns_grid_desc* gd, const ns_params* p) {
         // the residual 3-sweep pass, every rank's slab at least deep_e + 3 rows (one neighbour feeds the exchange)
         // (E1 = 8 + 6 R: the residual pass's 7-row cone plus the one row of each neighbour it computes for K3)
         const int R = std::max(1, s->band_sweeps / 3), E1 = 8 + 6 * R;
-        bool ok = p->nranks > 1 && !masked && s->fps && k.helm_band && k.sweep3 && k.sweep3_res && s->triple && k.deep;
+        bool ok = p->nranks > 1 && !masked && s->fps && k.helm_band && k.sweep3 && k.sweep3_res && k.deep;
         for (int q = 0; q < p->nranks && ok; q++) {
             int32_t a0, a1;
             ns_slab_range(g.nx, p->nranks, q, &a0, &a1);
@@ -3938,9 +3941,9 @@ int choose_paths(ns_solver* s, const ns_grid_desc* gd, const ns_params* p) {
                      nsg::correct_streams(k, g) && k.k5_defer;
     if (k.verbose)
         fprintf(stderr, "nsgpu rank %d/%d: %d x %d, rows %d; direct solve %d (outflow %d, fused K3 %d), wall bands %d "
-                "(%d sweeps, %d wide), 3-sweep passes %d (residual %d, triple %d), deep ghost rows %d (%d)\n",
+                "(%d sweeps, %d wide), 3-sweep passes %d (residual %d), deep ghost rows %d (%d)\n",
                 s->rank, s->nranks, g.nx, g.ny, g.nxl, (int)s->fps, s->fa.outE, (int)s->fps_fuse, (int)k.helm_band,
-                s->band_sweeps, s->band_w, (int)k.sweep3, (int)k.sweep3_res, (int)s->triple, (int)s->deep,
+                s->band_sweeps, s->band_w, (int)k.sweep3, (int)k.sweep3_res, (int)s->deep,
                 s->deep_e);
     return 0;
 }

@@ -99,7 +99,10 @@ def test_direct_solve_x_stretched_matches_oracle(gpu, nx, ny, xr):
 
 
 @pytest.mark.parametrize("nx,ny,xr,yr", [(64, 64, -1, 1.03), (100, 96, 1.02, 0.98), (33, 44, -1, -1), (48, 22, 1.05, -1),
-                                        (256, 512, 1.001, 1.0005), (40, 2048, -1, 1.0002)])
+                                        (256, 512, 1.001, 1.0005), (40, 2048, -1, 1.0002),
+                                        # odd and tiny ny (a 63-, 7-, 3- and 2-point eigenvector transform), two rows
+                                        (40, 63, -1, -1), (5, 7, -1, -1), (2, 2, -1, -1), (9, 2, -1, -1),
+                                        (7, 3, 1.05, -1)])
 def test_direct_solve_dense_matches_krylov(gpu, nx, ny, xr, yr):
     """(r6) Every other walled rectangle the reference's Grid accepts: hy stretched (Grid.cpp:87-92) or an ny no FFT
     plan takes (44 = 4 x 11, 22) -- the transforms along y are Ly's eigenvectors (rocSOLVER's tridiagonal eigensolver
