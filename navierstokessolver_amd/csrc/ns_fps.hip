@@ -2248,7 +2248,8 @@ void launch_fps_t3(const FpsArgs& a, double* f, hipStream_t st) {
 // L_ext (the masked operator on the domain, zero-flux at its inner walls) differs from the bounding box's L_box
 // only across the m interface faces f = (i in the domain, j outside): L_box = L_ext - D_w D^T, d_f = e_i - e_j,
 // D_w's columns w_f d_f.  L_ext x = q is then x = L_box^+ (q - D_w y) with (I + D^T L_box^+ D_w) y = D^T L_box^+ q;
-// the capacitance matrix C is singular along y0 = 1 (the domain's constant), C + 1 1^T / m is not (CapArgs)
+// the capacitance matrix C is singular along y_c, the indicator of the faces that touch the connected component c of
+// the cells outside (one null vector per component; one component: y = 1), C + sum_c y_c y_c^T / m_c is not (CapArgs)
 namespace {
 
 // y = Cinv (D^T z): one row per wave; every workgroup gathers the m interface differences into LDS first
@@ -2323,7 +2324,8 @@ __global__ void k_cap_src(CapArgs a, double* __restrict__ q, int fprev, int f) {
     if (f >= 0) { q[a.fi[f]] = a.w[f]; q[a.fj[f]] = -a.w[f]; }
 }
 
-// set-up: column f of C + 1 1^T / m from z = L_box^+ (w_f d_f) (row-major in cmat); bordered, its row m = 1
+// set-up: column f of C + sum_c y_c y_c^T / m_c from z = L_box^+ (w_f d_f) (row-major in cmat: + 1 / m_c where rows
+// r and f touch the same outside component, all of them where there is one); bordered, its row m = 1
 // (y0^T y = 0), and column f = m from z = L_box^+ 1_domain: -D^T z, 0
 __global__ __launch_bounds__(256) void k_cap_col(CapArgs a, const double* __restrict__ z, int f,
                                                  double* __restrict__ cmat) {
@@ -2332,11 +2334,11 @@ __global__ __launch_bounds__(256) void k_cap_col(CapArgs a, const double* __rest
     double val;
     if (r == a.m) val = f < a.m ? 1.0 : 0.0;
     else if (f == a.m) val = -(z[a.fi[r]] - z[a.fj[r]]);
-    else val = (r == f ? 1.0 : 0.0) + (z[a.fi[r]] - z[a.fj[r]]) + 1.0 / a.m;
+    else val = (r == f ? 1.0 : 0.0) + (z[a.fi[r]] - z[a.fj[r]]) + (a.fk[r] == a.fk[f] ? 1.0 / a.fm[f] : 0.0);
     cmat[(size_t)r * M + f] = val;
 }
 
-// set-up: Gauss-Jordan inversion in place without pivoting (C + 1 1^T / m is symmetric positive definite for
+// set-up: Gauss-Jordan inversion in place without pivoting (the regularised C is symmetric positive definite for
 // uniform face weights, a diagonal similarity of one otherwise): pivot k's scaled row t and column u ...
 // (r6) flagged -- the caller then keeps the preconditioned BiCGStab -- when a pivot is not finite, below
 // GJ_TINY in magnitude (C's entries are O(1): the identity plus the dipoles' responses), or, without a border (spd),

@@ -449,16 +449,17 @@ void launch_fps_scan(const FpsArgs& a, bool backward, const FpsRank& R, double* 
 
 // (r5) a masked domain's exact Poisson solve by the capacitance matrix of its interface with the bounding box
 // (ns_fps.hip; ns_solver.cpp cap_setup / cap_solve): m faces (fi: the domain cell's plane offset, fj: the outside
-// cell's, w: the face's operator weight), cinv = (C + 1 1^T / m)^-1 (m x m, row-major), y (m); the ncell cells on
-// either side of a face (co: plane offset, cf: up to 4 signed face references +-(f + 1), + on the domain's side,
-// 0: none)
+// cell's, w: the face's operator weight; fk: the connected component of the box's outside cells the face touches,
+// fm: that component's face count m_c), cinv = (C + sum_c y_c y_c^T / m_c)^-1 (m x m, row-major; y_c the indicator
+// of component c's faces -- one component: 1 1^T / m), y (m); the ncell cells on either side of a face (co: plane
+// offset, cf: up to 4 signed face references +-(f + 1), + on the domain's side, 0: none)
 // (r5) border = 1: the box has the E outflow (mode 0 of its solve and of the domain's in the projected sense): the
 // system is bordered by the unknown constant lambda the domain's right-hand side takes (q + lambda 1_domain) and the
 // row y0^T y = 0 -- cinv is (m + 1) x (m + 1), y[m] = lambda, e1 = L_box^+ 1_domain (a plane)
 struct CapArgs {
     int m = 0, ncell = 0, border = 0;
     const double* e1 = nullptr;
-    const int *fi = nullptr, *fj = nullptr, *co = nullptr;
+    const int *fi = nullptr, *fj = nullptr, *fk = nullptr, *fm = nullptr, *co = nullptr;
     const int4* cf = nullptr;
     const double* w = nullptr;
     double *cinv = nullptr, *y = nullptr;

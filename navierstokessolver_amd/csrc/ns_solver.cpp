@@ -1819,9 +1819,10 @@ int fps_precond(ns_solver* s, const double* q, double* z, double* scratch, const
 }
 
 // (r5) z = L_ext^+ q on a masked domain by its capacitance matrix (nsg::CapArgs): two box solves around the
-// interface's dense m x m solve -- z1 = L_box^+ q, y = (C + 1 1^T / m)^-1 D^T z1, z = L_box^+ (q - D_w y).  q is mean-
-// free over the domain and 0 outside it (the residual k_bicg_vec's KV_INIT leaves); it is modified at the
-// interface cells and restored to 0 outside (its domain values are rewritten by the next KV_INIT)
+// interface's dense m x m solve -- z1 = L_box^+ q, y = (C + sum_c y_c y_c^T / m_c)^-1 D^T z1 (cap_setup),
+// z = L_box^+ (q - D_w y).  q is mean-free over the domain and 0 outside it (the residual k_bicg_vec's KV_INIT
+// leaves); it is modified at the interface cells and restored to 0 outside (its domain values are rewritten by the
+// next KV_INIT)
 // (r6) xout: the second box solve writes the solution's domain cells straight into xout (its other cells kept) --
 // the x = z pass of a solve from zero (k_cap_axpy, 57 us at 4096^2) not needed
 int cap_solve(ns_solver* s, double* q, double* z, double* xout = nullptr) {
@@ -1837,12 +1838,24 @@ int cap_solve(ns_solver* s, double* q, double* z, double* xout = nullptr) {
     return 0;
 }
 
+// whether a capacitance solve from x = 0 writes the solution's domain cells straight into x by the masked inverse
+// transform (cap_solve's xout): no border row, no E outflow, and that transform built for this ny.  bicgstab's choice
+// and cap_setup's verbose line both ask here
+static bool cap_direct_x(const ns_solver* s) {
+    return s->cap.m > 0 && !s->cap.border && !s->fa.outE && nsg::fps_idct_mask_ok(s->g.ny);
+}
+
 // (r5) the capacitance matrix of a masked domain on one rank whose bounding box has the direct solve: the m
 // faces between a domain cell and a box cell outside it, then C's columns by m box solves of the faces'
-// dipoles w_f d_f (C[g][f] = delta_gf + (D^T L_box^+ w_f d_f)_g, + 1 / m: the regularisation along the domain's
-// constant y0 = 1, C y0 = 0) and its inverse by Gauss-Jordan, all on the device.  Not built (BiCGStab with the box
-// preconditioner stays): m = 0 or > NSGPU_CAP_MAX (4096; clamped to the gemv's LDS bound, nsg::CAP_LDS_MAX - 1),
-// NSGPU_CAP=0, a Gauss-Jordan pivot that is not finite, below 1e-12 in magnitude, or (no border) not positive
+// dipoles w_f d_f (C[g][f] = delta_gf + (D^T L_box^+ w_f d_f)_g) and its inverse by Gauss-Jordan, all on the device.
+// C has one null vector per connected component c of the box's cells outside the domain (the extended operator's
+// constant on c): y_c, the indicator of the m_c faces that touch c.  The components come from a flood fill of the
+// outside cells (4-neighbours, here on the host) and C is regularised along each, + sum_c y_c y_c^T / m_c -- one
+// component (an L-shape, a notch, a step): + 1 / m in every entry; a T, a plus, a dumbbell, a channel with a
+// constriction: 2 to 4 blocks.  The bordered (E-outflow) system takes the same term and keeps its one row 1^T.
+// Not built (BiCGStab with the box preconditioner stays): m = 0 or > NSGPU_CAP_MAX (4096; clamped to the gemv's LDS
+// bound, nsg::CAP_LDS_MAX - 1), NSGPU_CAP=0, or -- a last resort no supported shape depends on -- a Gauss-Jordan
+// pivot that is not finite, below 1e-12 in magnitude, or (no border) not positive
 int cap_setup(ns_solver* s, const ns_grid_desc* gd, const double* pw, const double* pe, const double* ps,
               const double* pn) {
     if (!s->k.cap) return 0;
@@ -1850,7 +1863,7 @@ int cap_setup(ns_solver* s, const ns_grid_desc* gd, const double* pw, const doub
     const nsg::Geo& g = s->g;
     const int nx = gd->nx, ny = gd->ny;
     auto inside = [&](int i, int j) { return gd->cell_id[(size_t)i * ny + j] >= 0; };
-    std::vector<int> fi, fj;
+    std::vector<int> fi, fj, fo;   // (fo: the outside cell's index in the global box)
     std::vector<double> w;
     std::map<int, std::vector<int>> refs;   // plane offset -> signed face references
     const int di[4] = {-1, 1, 0, 0}, dj[4] = {0, 0, -1, 1};
@@ -1865,6 +1878,7 @@ int cap_setup(ns_solver* s, const ns_grid_desc* gd, const double* pw, const doub
                 const int oi = (i - g.i0) * g.ld + j, oj = (a - g.i0) * g.ld + b;
                 fi.push_back(oi);
                 fj.push_back(oj);
+                fo.push_back(a * ny + b);
                 // (the coefficient of this face in the domain cell's row; the same in the outside cell's row on the
                 // uniform grids the box's direct solve admits)
                 w.push_back(k == 0 ? pw[i] : k == 1 ? pe[i] : k == 2 ? ps[j] : pn[j]);
@@ -1874,6 +1888,31 @@ int cap_setup(ns_solver* s, const ns_grid_desc* gd, const double* pw, const doub
         }
     const int m = (int)fi.size();
     if (m == 0) return 0;
+    // the outside cells' connected components, and per face its component and that component's face count
+    std::vector<int> lab((size_t)nx * ny, -1), stack;
+    int ncomp = 0;
+    for (int s0 = 0; s0 < nx * ny; s0++) {
+        if (gd->cell_id[s0] >= 0 || lab[s0] >= 0) continue;
+        lab[s0] = ncomp;
+        stack.push_back(s0);
+        while (!stack.empty()) {
+            const int c = stack.back(), i = c / ny, j = c % ny;
+            stack.pop_back();
+            for (int k = 0; k < 4; k++) {
+                const int a = i + di[k], b = j + dj[k];
+                if (a < 0 || a >= nx || b < 0 || b >= ny || inside(a, b) || lab[(size_t)a * ny + b] >= 0) continue;
+                lab[(size_t)a * ny + b] = ncomp;
+                stack.push_back(a * ny + b);
+            }
+        }
+        ncomp++;
+    }
+    std::vector<int> fk(m), fm(m), mc(ncomp, 0);
+    for (int f = 0; f < m; f++) {
+        fk[f] = lab[fo[f]];
+        mc[fk[f]]++;
+    }
+    for (int f = 0; f < m; f++) fm[f] = mc[fk[f]];
     std::vector<int> co;
     std::vector<int> cf;
     for (const auto& kv : refs) {
@@ -1885,26 +1924,29 @@ int cap_setup(ns_solver* s, const ns_grid_desc* gd, const double* pw, const doub
     // (an E outflow: the bordered system, M = m + 1, and the plane e1 = L_box^+ 1_domain)
     const int border = s->fa.outE ? 1 : 0, M = m + border;
     const size_t ne1 = border ? s->plane : 0;
-    // device: cinv (M^2), y, t, u (M each), w (m), flag, e1 (doubles); fi, fj, co, cf (ints)
+    // device: cinv (M^2), y, t, u (M each), w (m), flag, e1 (doubles); fi, fj, fk, fm, co, cf (ints)
     // (nd even and the int4 table at a multiple of 4 ints: 16-byte aligned)
-    const size_t nd = ((size_t)M * M + 4 * (size_t)M + ne1 + 9) & ~(size_t)1, o4 = (2 * (size_t)m + nc + 3) & ~(size_t)3;
+    const size_t nd = ((size_t)M * M + 4 * (size_t)M + ne1 + 9) & ~(size_t)1;
+    const size_t o4 = (4 * (size_t)m + nc + 3) & ~(size_t)3;
     const size_t ni = o4 + 4 * (size_t)nc;
     HIPCHK(hipMalloc(&s->cap_mem, nd * sizeof(double) + ni * sizeof(int)));
     double* dm = (double*)s->cap_mem;
     double *cinv = dm, *y = cinv + (size_t)M * M, *wd = y + M, *t = wd + M, *u = t + M, *flag = u + M;
     double* e1 = border ? flag + 8 + (size_t)s->hp * g.ld : nullptr;
     int* im = (int*)(dm + nd);
-    int *dfi = im, *dfj = dfi + m, *dco = dfj + m;
+    int *dfi = im, *dfj = dfi + m, *dfk = dfj + m, *dfm = dfk + m, *dco = dfm + m;
     int* dcf = im + o4;
     HIPCHK(hipMemcpy(wd, w.data(), m * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemset(flag, 0, sizeof(double)));
     HIPCHK(hipMemcpy(dfi, fi.data(), m * sizeof(int), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dfj, fj.data(), m * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dfk, fk.data(), m * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dfm, fm.data(), m * sizeof(int), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dco, co.data(), nc * sizeof(int), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dcf, cf.data(), 4 * (size_t)nc * sizeof(int), hipMemcpyHostToDevice));
     nsg::CapArgs& a = s->cap;
     a.m = m; a.ncell = nc; a.border = border; a.e1 = e1;
-    a.fi = dfi; a.fj = dfj; a.co = dco; a.cf = (const int4*)dcf; a.w = wd;
+    a.fi = dfi; a.fj = dfj; a.fk = dfk; a.fm = dfm; a.co = dco; a.cf = (const int4*)dcf; a.w = wd;
     a.cinv = cinv; a.y = y;
     // C by columns: the dipole in the (zeroed) plane kv[0], its box solve into kv[6]
     HIPCHK(hipStreamSynchronize(s->st));   // (the Krylov planes' memset)
@@ -1926,16 +1968,18 @@ int cap_setup(ns_solver* s, const ns_grid_desc* gd, const double* pw, const doub
     HIPCHK(hipStreamSynchronize(s->st));
     if (fl != 0.0) {   // (never seen: the preconditioned BiCGStab instead)
         if (s->k.verbose)
-            fprintf(stderr, "nsgpu: capacitance matrix (%d faces): a Gauss-Jordan pivot failed the test of k_gj_prep "
-                            "(not finite, tiny%s): BiCGStab\n", m, border ? "" : " or not positive");
+            fprintf(stderr, "nsgpu: capacitance matrix (%d faces, %d outside component%s): a Gauss-Jordan pivot failed "
+                            "the test of k_gj_prep (not finite, tiny%s): BiCGStab\n", m, ncomp, ncomp == 1 ? "" : "s",
+                    border ? "" : " or not positive");
         s->cap = nsg::CapArgs{};
         (void)hipFree(s->cap_mem);
         s->cap_mem = nullptr;
         return 0;
     }
     if (s->k.verbose)
-        fprintf(stderr, "nsgpu: masked Poisson by the capacitance matrix: %d interface faces, %d cells%s\n", m, nc,
-                border ? ", bordered (E outflow)" : "");
+        fprintf(stderr, "nsgpu: masked Poisson by the capacitance matrix: %d interface faces, %d cells, %d outside "
+                        "component%s%s%s\n", m, nc, ncomp, ncomp == 1 ? "" : "s",
+                border ? ", bordered (E outflow)" : "", cap_direct_x(s) ? ", masked inverse transform" : "");
     return 0;
 }
 
@@ -2032,7 +2076,7 @@ int bicgstab(ns_solver* s, const KrylovSolve& ks, int* its, double* res) {
         if (s->in_step) s->fps_solves++;
         for (;;) {
             // (the first from x = 0 without a border row: the solution's domain cells written straight into x)
-            const bool direct_x = its0 == 0 && !s->cap.border && nsg::fps_idct_mask_ok(s->g.ny) && !s->fa.outE;
+            const bool direct_x = its0 == 0 && cap_direct_x(s);
             if (direct_x) {
                 CHK(cap_solve(s, a.r, s->kv[6], a.x));
             } else {

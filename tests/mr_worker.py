@@ -47,8 +47,8 @@ try:
     if a.poly:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         from oracle import OGrid   # the geometry's spacings (a test helper, not the solve)
-        from polygons import ALL
-        P = ALL[a.poly]
+        from polygons import ALL, NARROW
+        P = {**ALL, **NARROW}[a.poly]
         og = OGrid(P["vertices"], P["xspec"], P["yspec"], P["bc"])
         n, ny = og.nx, og.ny
         grid = nsa.polygon(P["vertices"], og.hx, og.hy, P["bc"])

@@ -5,12 +5,14 @@ import pytest
 
 import navierstokessolver_amd as nsa
 from oracle import OGrid
-from polygons import ALL
+from polygons import ALL, NARROW, NARROW_TALL, SPLITS
+
+POLY = {**ALL, **NARROW, **NARROW_TALL, **SPLITS}
 
 
-@pytest.mark.parametrize("name", sorted(ALL))
+@pytest.mark.parametrize("name", sorted(ALL) + sorted(NARROW) + sorted(NARROW_TALL) + sorted(SPLITS))
 def test_polygon_classifier_matches_oracle(name):
-    P = ALL[name]
+    P = POLY[name]
     og = OGrid(P["vertices"], P["xspec"], P["yspec"], P["bc"])
     gs = nsa.polygon(P["vertices"], og.hx, og.hy, P["bc"])
     assert gs.cell_id is not None
