@@ -275,6 +275,33 @@ int  ns_time_poisson(ns_solver* s, int warmup, int iters, double* out);
  * use, 3 x 4 B/cell); out[0..2] as above, out[3] = residual^2 of the last sweep's input. */
 int  ns_time_poisson_fp32(ns_solver* s, int warmup, int iters, double* out);
 
+/* ---- passive scalar (temperature / dye / concentration) carried by the time step ----
+ * An optional field T advanced inside ns_step / ns_step_async by the velocities' scheme: AB2 on the MUSCL /
+ * Rusanov convective term div(u T), Crank-Nicolson diffusion with the Peclet number pe in re's place, no
+ * pressure term, no coupling back into momentum ("Passive scalar").  A solver without a scalar
+ * runs exactly the launches it ran before.  Additive to ABI 9: no struct above changes, the scalar's planes
+ * are allocated by ns_scalar_enable (not counted by ns_device_bytes).  One rank's rectangle only
+ * (INTEGRATION.md 4): a masked polygon (cell_id != NULL) and nranks > 1 are refused. */
+#define NS_SBC_DIRICHLET 0   /* T = value on the edge */
+#define NS_SBC_ZEROGRAD  1   /* adiabatic wall / outflow */
+typedef struct ns_scalar_bc   { int32_t type; double value; } ns_scalar_bc;
+typedef struct ns_scalar_desc { double pe; int32_t n_edges; const ns_scalar_bc* bc; } ns_scalar_desc; /* bc[k] for grid edge k */
+typedef struct ns_scalar_stats {
+    double  tmin, tmax;          /* of T after the step */
+    int32_t it_t;                /* sweeps of the scalar's Helmholtz solve */
+    double  res_t;               /* its final relative residual */
+    double  t_rhs_kernel_ms;     /* the right-hand side kernel's duration (k_rhs_t; timing == 1) */
+    int32_t n_rhs_kernels;       /* launches timed (0 or 1) */
+} ns_scalar_stats;
+int  ns_scalar_enable(ns_solver* s, const ns_scalar_desc* d);            /* T = 0, cT0 = 0; once per solver */
+int  ns_scalar_set(ns_solver* s, const double* T, const double* cT0);    /* compact-id order, either may be NULL */
+int  ns_scalar_get(ns_solver* s, double* T, double* cT0);
+int  ns_scalar_last(ns_solver* s, ns_scalar_stats* out);                 /* the latest completed step's */
+/* tests: which = 1 the right-hand side alone (cT0 <- cT, rT readable by ns_scalar_get_rhs; out[0] = ||rT||^2),
+ * 2 = the converged solve of the current rT from the current T (out[0] = sweeps, out[1] = relative residual) */
+int  ns_scalar_kernel(ns_solver* s, int which, double* out);
+int  ns_scalar_get_rhs(ns_solver* s, double* rT);
+
 /* ---- host-side helpers (no GPU needed) ---- */
 /* the x-slab [i0, i1) of `rank` out of `nranks` for nx cells */
 int  ns_slab_range(int32_t nx, int32_t nranks, int32_t rank, int32_t* i0, int32_t* i1);

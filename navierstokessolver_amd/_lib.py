@@ -81,6 +81,25 @@ class NsStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+NS_SBC_DIRICHLET, NS_SBC_ZEROGRAD = 0, 1
+
+
+class NsScalarBc(ctypes.Structure):
+    _fields_ = [("type", ctypes.c_int32), ("value", ctypes.c_double)]
+
+
+class NsScalarDesc(ctypes.Structure):
+    _fields_ = [("pe", ctypes.c_double), ("n_edges", ctypes.c_int32), ("bc", ctypes.POINTER(NsScalarBc))]
+
+
+class NsScalarStats(ctypes.Structure):
+    _fields_ = [("tmin", ctypes.c_double), ("tmax", ctypes.c_double), ("it_t", ctypes.c_int32),
+                ("res_t", ctypes.c_double), ("t_rhs_kernel_ms", ctypes.c_double), ("n_rhs_kernels", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _P = ctypes.c_void_p
 _D = ctypes.POINTER(ctypes.c_double)
 SIGNATURES = {
@@ -100,6 +119,12 @@ SIGNATURES = {
     "ns_time_poisson": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _D]),
     "ns_time_poisson_fp32": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _D]),
     "ns_set_timing": (ctypes.c_int, [_P, ctypes.c_int]),
+    "ns_scalar_enable": (ctypes.c_int, [_P, ctypes.POINTER(NsScalarDesc)]),
+    "ns_scalar_set": (ctypes.c_int, [_P, _D, _D]),
+    "ns_scalar_get": (ctypes.c_int, [_P, _D, _D]),
+    "ns_scalar_last": (ctypes.c_int, [_P, ctypes.POINTER(NsScalarStats)]),
+    "ns_scalar_kernel": (ctypes.c_int, [_P, ctypes.c_int, _D]),
+    "ns_scalar_get_rhs": (ctypes.c_int, [_P, _D]),
     "ns_slab_range": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                      ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "ns_nccl_id_size": (ctypes.c_int, []),

@@ -92,6 +92,14 @@ struct Partials {
 int launch_rhs(const Knobs& kn, const Geo& g, const Coef& c, double dt, double re, const double* u, const double* v,
                const double* phi, double* cu, double* cv, double* ru, double* rv, double* part, hipStream_t st,
                int depth = 2, double* uo = nullptr, double* vo = nullptr, double* mm = nullptr);
+// the passive scalar's right-hand side (k_rhs_t; NSGPU_CELL=grid: k_rhs_t_grid, thread per cell): q = T, cq = cT0 ->
+// cT in place, rq = rT; tneu / tc: the scalar's ghost per side, q_g = tneu ? q : -q + tc; partials sum rT^2, one
+// per block (the count is returned).  One rank's rectangle only (-1 otherwise)
+int launch_rhs_t(const Knobs& kn, const Geo& g, const Coef& c, const int* tneu, const double* tc, double dt, double pe,
+                 const double* u, const double* v, const double* q, double* cq, double* rq, double* part,
+                 hipStream_t st);
+// (min, -max) partials of a plane's own cells, 2 per block (launch_reduce_min's layout)
+int launch_minmax(const Geo& g, const double* f, double* part, hipStream_t st);
 // K2: fused red-black SOR sweep of (I - a L_V) on u and v, (u,v) -> (uo,vo);
 //     residual^2 partials of the input if part != null: u at part[0..n), v at part[n..2n), n returned
 int launch_helm_sweep(const Knobs& kn, const Geo& g, const Coef& c, double alpha, double omega, const double* u, const double* v,

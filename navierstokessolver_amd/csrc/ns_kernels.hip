@@ -1519,6 +1519,29 @@ struct RhsRingArgs {
     int ncol, jhi;                // ring columns per other row: 0, 1, jhi .. ny-1
     int rlo, rhi;                 // the other rows: local [rlo, rhi)
     int n;                        // ring cells
+    // ring cell k (< n) -> its local row and column
+    __device__ __forceinline__ void cell(int k, int ny, int& li, int& j) const {
+        const int nf = nfull * ny;
+        if (k < nf) {
+            const int q = k / ny;
+            li = fr[q];
+            j = k - q * ny;
+        } else {
+            const int q = (k - nf) / ncol, e = (k - nf) - q * ncol;
+            li = rlo + q;
+            j = e < 2 ? e : jhi + (e - 2);
+        }
+    }
+    // host: the ring of the strips that write rows [ilo, ihi) x columns [2, jhi_) of an nxl x ny slab
+    void plan(int nxl, int ny, int ilo, int ihi, int jhi_) {
+        jhi = jhi_;
+        for (int li = 0; li < nxl; li++)
+            if ((li < ilo || li >= ihi) && nfull < 4) fr[nfull++] = li;
+        rlo = ilo;
+        rhi = ihi;
+        ncol = jhi <= 2 ? ny : 2 + (ny - jhi);   // (tiny grids: whole rows)
+        n = nfull * ny + (rhi - rlo) * ncol;
+    }
 };
 struct RhsStreamArgs {
     Geo g;
@@ -1551,16 +1574,7 @@ __device__ __forceinline__ void rhs_ring_body(const Geo& g, const Coef& c, doubl
     double amm[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
     if (k < R.n) {
         int li, j;
-        const int nf = R.nfull * g.ny;
-        if (k < nf) {
-            const int q = k / g.ny;
-            li = R.fr[q];
-            j = k - q * g.ny;
-        } else {
-            const int q = (k - nf) / R.ncol, e = (k - nf) - q * R.ncol;
-            li = R.rlo + q;
-            j = e < 2 ? e : R.jhi + (e - 2);
-        }
+        R.cell(k, g.ny, li, j);
         const int ld = g.ld, gi = g.i0 + li;
         const ptrdiff_t o = (ptrdiff_t)li * ld + j;
         // (CORR: the stencil's u, v corrected from u*, v* and phi^n on the fly, each value by corr_at)
@@ -1919,6 +1933,359 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
 // stencil's wall cases and the ApplyBoundaryConditions terms), global loads; partials (ru^2, rv^2)
 // per block.  Thread k: the whole wall rows first (nfull of them, from local row fr[q]), then
 // (ncol columns) x the other rows.
+
+// ---------------------------------------------------------------- passive scalar: its right-hand side
+// A scalar T carried by the flow ("Passive scalar"): AB2 on the MUSCL / Rusanov convective term
+// div(u T), Crank-Nicolson diffusion with the Peclet number in Re's place, no pressure term.  Per face the
+// normal velocity's two states (n1, n2: K1's own face states of u on x-faces, of v on y-faces) and the
+// scalar's (t1, t2: rhs_cell's MUSCL states with the scalar's ghosts) give F = 0.5 (n1 t1 + n2 t2 -
+// |n1 + n2| (t2 - t1)) -- fnn for T = u.  The expressions a compiler may contract into FMAs live in the
+// sc_* helpers below with contraction off, and every path -- the strips, their wall ring, the
+// thread-per-cell kernel -- goes through them: the paths agree bit for bit, not up to contraction.
+__device__ __forceinline__ double sc_up(double q, double h, double s) {
+#pragma clang fp contract(off)
+    return q + h / 2 * s;
+}
+__device__ __forceinline__ double sc_dn(double q, double h, double s) {
+#pragma clang fp contract(off)
+    return q - h / 2 * s;
+}
+__device__ __forceinline__ double sc_flux(double n1, double n2, double t1, double t2) {
+#pragma clang fp contract(off)
+    return 0.5 * (n1 * t1 + n2 * t2 - fabs(n1 + n2) * (t2 - t1));
+}
+// rT = T + 0.5 dt cT0 + dt div(D) - 1.5 dt cT with cT = div(F); D0..D3 / F0..F3: the W, E, S, N faces
+__device__ __forceinline__ void sc_finish(double tc, double c0, double D0, double D1, double D2, double D3, double F0,
+                                          double F1, double F2, double F3, double rx, double ry, double dt,
+                                          double& cn, double& r) {
+#pragma clang fp contract(off)
+    r = tc + 0.5 * dt * c0;
+    r += dt * ((D1 - D0) * rx + (D3 - D2) * ry);
+    cn = (F1 - F0) * rx + (F3 - F2) * ry;
+    r += cn * (-1.5 * dt);
+}
+// the implicit half's ghost constant of a Dirichlet face (rhs_bc's wall term without its phi part)
+__device__ __forceinline__ double sc_wall(double r, double dt, double hpe, double h, double c) {
+#pragma clang fp contract(off)
+    return r + dt * (hpe / (h * h)) * c;
+}
+
+// the scalar's ghosts: across face k (0 W, 1 E, 2 S, 3 N) q_g = neu[k] ? q : -q + c[k] (c = 2 x the Dirichlet
+// value).  Rectangles: per side; the topology argument is where a masked domain's per-edge table would go
+struct ScalarBC {
+    int neu[4];
+    double c[4];
+    template <class T>
+    __device__ __forceinline__ double ghost(const T&, int, int, int k, double q) const { return neu[k] ? q : -q + c[k]; }
+    template <class T>
+    __device__ __forceinline__ bool dirichlet(const T&, int k, double& cc) const { cc = c[k]; return !neu[k]; }
+};
+
+// one cell of the scalar's right-hand side: U / V / Q(di, dj) the velocities and the scalar at offsets, X / Y the
+// spacing tables as rhs_cell takes them; c0 the previous step's convective term; returns the new one and rT
+template <class T = TopoRect, class FU, class FV, class FQ, class FX, class FY>
+__device__ __forceinline__ void scalar_cell(const Geo& g, const ScalarBC& B, double dt, double pe, FU&& U, FV&& V,
+                                            FQ&& Q, FX&& X, FY&& Y, int li, int j, double c0, double& cn, double& r) {
+    const T t(g, li, j);
+    const bool hW = t.in(-1, 0), hWW = hW && t.in(-2, 0), hE = t.in(1, 0), hEE = hE && t.in(2, 0);
+    const bool hS = t.in(0, -1), hSS = hS && t.in(0, -2), hN = t.in(0, 1), hNN = hN && t.in(0, 2);
+    const double hx = X(0, 0), hy = Y(0, 0);
+    const double hxW = hW ? X(0, -1) : 0.0, hxE = hE ? X(0, 1) : 0.0;
+    const double hyS = hS ? Y(0, -1) : 0.0, hyN = hN ? Y(0, 1) : 0.0;
+    const double rx = X(1, 0), ry = Y(1, 0);
+    const double rxW = hW ? X(1, -1) : 0.0, rxE = hE ? X(1, 1) : 0.0;
+    const double ryS = hS ? Y(1, -1) : 0.0, ryN = hN ? Y(1, 1) : 0.0;
+    const double sxW = X(2, 0), sxE = X(2, 1), sxWW = hW ? X(2, -1) : 0.0, sxEE = hE ? X(2, 2) : 0.0;
+    const double syS = Y(2, 0), syN = Y(2, 1), sySS = hS ? Y(2, -1) : 0.0, syNN = hN ? Y(2, 2) : 0.0;
+
+    const double uc = U(0, 0), uW = hW ? U(-1, 0) : 0.0, uE = hE ? U(1, 0) : 0.0;
+    const double uWW = hWW ? U(-2, 0) : 0.0, uEE = hEE ? U(2, 0) : 0.0;
+    const double vc = V(0, 0), vS = hS ? V(0, -1) : 0.0, vN = hN ? V(0, 1) : 0.0;
+    const double vSS = hSS ? V(0, -2) : 0.0, vNN = hNN ? V(0, 2) : 0.0;
+    const double qc = Q(0, 0), qW = hW ? Q(-1, 0) : 0.0, qE = hE ? Q(1, 0) : 0.0, qS = hS ? Q(0, -1) : 0.0,
+                 qN = hN ? Q(0, 1) : 0.0;
+    const double qWW = hWW ? Q(-2, 0) : 0.0, qEE = hEE ? Q(2, 0) : 0.0, qSS = hSS ? Q(0, -2) : 0.0,
+                 qNN = hNN ? Q(0, 2) : 0.0;
+    auto gq = [&](int di, int dj, int k, double q) { return B.ghost(t, di, dj, k, q); };
+
+    // DiffusiveFlux with 0.5 / pe (rhs_cell's expressions)
+    const double hpe = 0.5 / pe;
+    const double D0 = hW ? hpe * (qc - qW) * sxW : hpe * rx * (qc - gq(0, 0, 0, qc));
+    const double D1 = hE ? hpe * (qE - qc) * sxE : -hpe * rx * (qc - gq(0, 0, 1, qc));
+    const double D2 = hS ? hpe * (qc - qS) * syS : hpe * ry * (qc - gq(0, 0, 2, qc));
+    const double D3 = hN ? hpe * (qN - qc) * syN : -hpe * ry * (qc - gq(0, 0, 3, qc));
+
+    // the four faces: the normal velocity's states and the scalar's (rhs_cell's u1 / u2 of each face)
+    double F[4], n1, n2, t1, t2;
+    const double sxu = slope_r(uc, uE, uW, hE, hW, rx, sxE, sxW, t.gv(0, 0, 1, uc, 0), t.gv(0, 0, 0, uc, 0));
+    const double sxq = slope_r(qc, qE, qW, hE, hW, rx, sxE, sxW, gq(0, 0, 1, qc), gq(0, 0, 0, qc));
+    n2 = sc_dn(uc, hx, sxu);
+    t2 = sc_dn(qc, hx, sxq);
+    if (hW) {
+        n1 = sc_up(uW, hxW, slope_r(uW, uc, uWW, true, hWW, rxW, sxW, sxWW, 0.0, t.gv(-1, 0, 0, uW, 0)));
+        t1 = sc_up(qW, hxW, slope_r(qW, qc, qWW, true, hWW, rxW, sxW, sxWW, 0.0, gq(-1, 0, 0, qW)));
+    } else {
+        n1 = 0.5 * (uc + t.gv(0, 0, 0, uc, 0));
+        t1 = 0.5 * (qc + gq(0, 0, 0, qc));
+    }
+    F[0] = sc_flux(n1, n2, t1, t2);
+    n1 = sc_up(uc, hx, sxu);
+    t1 = sc_up(qc, hx, sxq);
+    if (hE) {
+        n2 = sc_dn(uE, hxE, slope_r(uE, uEE, uc, hEE, true, rxE, sxEE, sxE, t.gv(1, 0, 1, uE, 0), 0.0));
+        t2 = sc_dn(qE, hxE, slope_r(qE, qEE, qc, hEE, true, rxE, sxEE, sxE, gq(1, 0, 1, qE), 0.0));
+    } else {
+        n2 = 0.5 * (uc + t.gv(0, 0, 1, uc, 0));
+        t2 = 0.5 * (qc + gq(0, 0, 1, qc));
+    }
+    F[1] = sc_flux(n1, n2, t1, t2);
+    const double syv = slope_r(vc, vN, vS, hN, hS, ry, syN, syS, t.gv(0, 0, 3, vc, 1), t.gv(0, 0, 2, vc, 1));
+    const double syq = slope_r(qc, qN, qS, hN, hS, ry, syN, syS, gq(0, 0, 3, qc), gq(0, 0, 2, qc));
+    n2 = sc_dn(vc, hy, syv);
+    t2 = sc_dn(qc, hy, syq);
+    if (hS) {
+        n1 = sc_up(vS, hyS, slope_r(vS, vc, vSS, true, hSS, ryS, syS, sySS, 0.0, t.gv(0, -1, 2, vS, 1)));
+        t1 = sc_up(qS, hyS, slope_r(qS, qc, qSS, true, hSS, ryS, syS, sySS, 0.0, gq(0, -1, 2, qS)));
+    } else {
+        n1 = 0.5 * (vc + t.gv(0, 0, 2, vc, 1));
+        t1 = 0.5 * (qc + gq(0, 0, 2, qc));
+    }
+    F[2] = sc_flux(n1, n2, t1, t2);
+    n1 = sc_up(vc, hy, syv);
+    t1 = sc_up(qc, hy, syq);
+    if (hN) {
+        n2 = sc_dn(vN, hyN, slope_r(vN, vNN, vc, hNN, true, ryN, syNN, syN, t.gv(0, 1, 3, vN, 1), 0.0));
+        t2 = sc_dn(qN, hyN, slope_r(qN, qNN, qc, hNN, true, ryN, syNN, syN, gq(0, 1, 3, qN), 0.0));
+    } else {
+        n2 = 0.5 * (vc + t.gv(0, 0, 3, vc, 1));
+        t2 = 0.5 * (qc + gq(0, 0, 3, qc));
+    }
+    F[3] = sc_flux(n1, n2, t1, t2);
+    sc_finish(qc, c0, D0, D1, D2, D3, F[0], F[1], F[2], F[3], rx, ry, dt, cn, r);
+    const bool bnd[4] = {!hW, !hE, !hS, !hN};
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        double cc;
+        if (bnd[k] && B.dirichlet(t, k, cc)) r = sc_wall(r, dt, hpe, k < 2 ? hx : hy, cc);
+    }
+}
+
+// the thread-per-cell form (NSGPU_CELL=grid): the strips' equivalence oracle; partials sum rT^2 per block
+__global__ __launch_bounds__(256) void k_rhs_t_grid(Geo g, Coef c, ScalarBC B, double dt, double pe,
+                                                    const double* __restrict__ u, const double* __restrict__ v,
+                                                    const double* __restrict__ q, double* __restrict__ cq,
+                                                    double* __restrict__ rq, double* __restrict__ part, int rows) {
+    const int j = blockIdx.x * 64 + threadIdx.x;
+    const int lend = min((int)(blockIdx.y + 1) * 4 * rows, g.nxl);
+    double acc[1] = {0.0};
+    for (int li = blockIdx.y * 4 * rows + threadIdx.y; li < lend && j < g.ny; li += 4) {
+        const int ld = g.ld, gi = g.i0 + li;
+        const ptrdiff_t o = (ptrdiff_t)li * ld + j;
+        auto U = [&](int di, int dj) { return ldf(u, ld, li + di, j + dj); };
+        auto V = [&](int di, int dj) { return ldf(v, ld, li + di, j + dj); };
+        auto Q = [&](int di, int dj) { return ldf(q, ld, li + di, j + dj); };
+        auto X = [&](int t, int d) { return (t == 0 ? c.hx : t == 1 ? c.rhx : c.rsx)[gi + d]; };
+        auto Y = [&](int t, int d) { return (t == 0 ? c.hy : t == 1 ? c.rhy : c.rsy)[j + d]; };
+        double cn, r;
+        scalar_cell<TopoRect>(g, B, dt, pe, U, V, Q, X, Y, li, j, cq[o], cn, r);
+        cq[o] = cn;
+        rq[o] = r;
+        acc[0] += r * r;
+    }
+    block_reduce_sum<1>(acc, part + (blockIdx.x + gridDim.x * blockIdx.y));
+}
+
+// k_rhs_t: the scalar's right-hand side as k_rhs_s's strips.  A wave owns 128 columns (2 per lane, 124
+// written) and walks L rows with SK rows in flight; when row r arrives (u, T at row r, v and cT0 at the output
+// row r-2), row r-1's x-slopes of u and T are formed, then the x-face (r-2 | r-1) -- its flux once, the E
+// face of row r-2 and the W face of row r-1 -- and row r-2 is complete: its y-faces come from that row's v
+// and T slopes across the lanes.  Per cell u, v, T, cT0 are read and cT (in place), rT written: 48 B, one
+// HBM pass.  The cells within two of a wall (and an odd ny's last column) are the ring's, scalar_cell per
+// cell in extra workgroups of the same launch, as K1's.  Partials: sum rT^2 per strip, then per ring block.
+struct RhsTArgs {
+    Geo g;
+    Coef c;
+    ScalarBC B;
+    double dt, pe;
+    const double *u, *v, *q;
+    double *cq, *rq;
+    double* part;
+    int nsj;
+    RowPlan P;
+    int ilo, ihi, jhi;            // written cells: local rows [ilo, ihi), columns [2, jhi)
+    int nsblk, nring, nstr;
+    RhsRingArgs R;
+};
+__device__ __forceinline__ void rhs_t_ring(const RhsTArgs& A, int blk) {
+    const Geo& g = A.g;
+    const Coef& c = A.c;
+    const RhsRingArgs& R = A.R;
+    const int k = blk * 256 + threadIdx.x;
+    double acc[1] = {0.0};
+    if (k < R.n) {
+        int li, j;
+        R.cell(k, g.ny, li, j);
+        const int ld = g.ld, gi = g.i0 + li;
+        const ptrdiff_t o = (ptrdiff_t)li * ld + j;
+        auto U = [&](int di, int dj) { return ldf(A.u, ld, li + di, j + dj); };
+        auto V = [&](int di, int dj) { return ldf(A.v, ld, li + di, j + dj); };
+        auto Q = [&](int di, int dj) { return ldf(A.q, ld, li + di, j + dj); };
+        auto X = [&](int t, int d) { return (t == 0 ? c.hx : t == 1 ? c.rhx : c.rsx)[gi + d]; };
+        auto Y = [&](int t, int d) { return (t == 0 ? c.hy : t == 1 ? c.rhy : c.rsy)[j + d]; };
+        double cn, r;
+        scalar_cell<TopoRect>(g, A.B, A.dt, A.pe, U, V, Q, X, Y, li, j, A.cq[o], cn, r);
+        A.cq[o] = cn;
+        A.rq[o] = r;
+        acc[0] = r * r;
+    }
+    block_reduce_sum<1>(acc, A.part + A.nstr + blk);
+}
+// rows in flight (A/B: make variant DEFS=-DRHS_T_SK=n)
+#ifndef RHS_T_SK
+#define RHS_T_SK 2
+#endif
+template <bool NT, int SK>
+__global__ __launch_bounds__(256) void k_rhs_t(RhsTArgs A) {
+    const Geo& g = A.g;
+    const Coef& c = A.c;
+    if ((int)blockIdx.x >= A.nsblk) {   // the wall ring's workgroups, after the strips' (block-uniform)
+        rhs_t_ring(A, (int)blockIdx.x - A.nsblk);
+        return;
+    }
+    const int sbx = (int)blockIdx.x;
+    // per row: hx, 1/hx, 2/(h_{i-1}+h_i), 2/(h_i+h_{i+1})
+    __shared__ double rcs[4][K1_LMAX + 2 * RC_K1 + 2][4];
+    const int lane = threadIdx.x & 63;
+    const int nstr = A.nsj * A.P.nrun;
+    const int w = xcd_swizzle(sbx, A.nsblk) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    double (*rc)[4] = rcs[threadIdx.x >> 6];
+    const int run = w / A.nsj, sj = w - run * A.nsj;
+    const int wid = (A.P.pbase + run) * A.nsj + sj;
+    int ib, ie;
+    A.P.rows(run, ib, ie);
+    if (w < nstr) {
+        for (int t = lane; t < ie - ib + 2 * RC_K1 + 2; t += 64) {
+            const int gi = min(max(g.i0 + ib - RC_K1 + t, 0), g.nx - 1);
+            rc[t][0] = c.hx[gi];
+            rc[t][1] = c.rhx[gi];
+            rc[t][2] = c.rsx[gi];
+            rc[t][3] = c.rsx[gi + 1];
+        }
+    }
+    __syncthreads();
+    double acc0 = 0.0;
+    if (w < nstr) {
+        const int ny = g.ny, ld = g.ld;
+        const int jb = sj * SW;
+        const int c0 = jb - 2 + 2 * lane;
+        const int lc = min(max(c0, 0), ld - 2);
+        const bool wr = lane >= 1 && lane <= 62 && c0 >= 2 && c0 < A.jhi;
+        // column tables (clamped; a clamped column only feeds unwritten lanes)
+        const int k0 = min(max(c0, 0), ny - 1), k1 = min(max(c0 + 1, 0), ny - 1), km = min(max(c0 - 1, 0), ny - 1);
+        const double hy0 = c.hy[k0], hy1 = c.hy[k1], hym = c.hy[km];
+        const double ry0 = c.rhy[k0], ry1 = c.rhy[k1];
+        const double rs0 = c.rsy[k0], rs1 = c.rsy[k1], rs2 = c.rsy[min(k1 + 1, ny)];
+        const double dt = A.dt, hpe = 0.5 / A.pe;
+        const int rlo = -HALO, rhi = g.nxl + HALO - 1;
+        const __amdgpu_buffer_rsrc_t bcq = __builtin_amdgcn_make_buffer_rsrc(A.cq, (short)0, 0x7FFFFFF0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t brq = __builtin_amdgcn_make_buffer_rsrc(A.rq, (short)0, 0x7FFFFFF0, 0x00020000);
+        // one row of u, T (row r) and of v, cT0 (row r-2, the output row of that step): SK rows in flight
+        double2 QU[SK], QT[SK], QV[SK], QC[SK];
+        auto load = [&](int r, double2& qu, double2& qt, double2& qv, double2& qc) {
+            const int lr = min(max(r, rlo), rhi), lo = min(max(r - 2, 0), g.nxl - 1);
+            qu = *reinterpret_cast<const double2*>(A.u + (ptrdiff_t)lr * ld + lc);
+            qt = *reinterpret_cast<const double2*>(A.q + (ptrdiff_t)lr * ld + lc);
+            qv = *reinterpret_cast<const double2*>(A.v + (ptrdiff_t)lo * ld + lc);
+            qc = *reinterpret_cast<const double2*>(A.cq + (ptrdiff_t)lo * ld + lc);
+        };
+        // windows: u rows r-2 .. r, T rows r-3 .. r; x-slopes of row r-2 (SP*); the x-face (r-3 | r-2)'s flux
+        double2 U1 = {0, 0}, U2 = {0, 0}, U3 = {0, 0};
+        double2 T0 = {0, 0}, T1 = {0, 0}, T2 = {0, 0}, T3 = {0, 0};
+        double2 SPu = {0, 0}, SPt = {0, 0}, FW = {0, 0};
+        auto xslope = [&](double qm, double qc, double qp, const double* rw) {
+            return minmode_nd((qp - qc) * rw[3], (qc - qm) * rw[2]);
+        };
+        auto step = [&](const double2 qu, const double2 qt, const double2 qv, const double2 c0v, int r) {
+            U1 = U2; U2 = U3; U3 = vcopy(qu);
+            T0 = T1; T1 = T2; T2 = T3; T3 = vcopy(qt);
+            const double* rm = rc[r - 2 - ib + RC_K1];   // output row m = r-2
+            const double* rn = rc[r - 1 - ib + RC_K1];   // row r-1
+            const double2 SCu = make_double2(xslope(U1.x, U2.x, U3.x, rn), xslope(U1.y, U2.y, U3.y, rn));
+            const double2 SCt = make_double2(xslope(T1.x, T2.x, T3.x, rn), xslope(T1.y, T2.y, T3.y, rn));
+            // x-face (r-2 | r-1): lower states from row r-2, upper from row r-1
+            const double hxm = rm[0], hxn = rn[0];
+            const double2 FE = make_double2(
+                sc_flux(sc_up(U1.x, hxm, SPu.x), sc_dn(U2.x, hxn, SCu.x), sc_up(T1.x, hxm, SPt.x), sc_dn(T2.x, hxn, SCt.x)),
+                sc_flux(sc_up(U1.y, hxm, SPu.y), sc_dn(U2.y, hxn, SCu.y), sc_up(T1.y, hxm, SPt.y), sc_dn(T2.y, hxn, SCt.y)));
+            // row m: y-slopes of v and T across the lanes (columns c0 - 1 .. c1 + 1)
+            const double vm = lane_up1(qv.y), vp = lane_dn1(qv.x), tm = lane_up1(T1.y), tp = lane_dn1(T1.x);
+            const double sv0 = minmode_nd((qv.y - qv.x) * rs1, (qv.x - vm) * rs0);
+            const double sv1 = minmode_nd((vp - qv.y) * rs2, (qv.y - qv.x) * rs1);
+            const double st0 = minmode_nd((T1.y - T1.x) * rs1, (T1.x - tm) * rs0);
+            const double st1 = minmode_nd((tp - T1.y) * rs2, (T1.y - T1.x) * rs1);
+            const double svm = lane_up1(sv1), stm = lane_up1(st1);   // column c0 - 1's slopes
+            // y-faces (c0-1 | c0) and (c0 | c1); (c1 | c1+1) from lane + 1
+            const double fa = sc_flux(sc_up(vm, hym, svm), sc_dn(qv.x, hy0, sv0), sc_up(tm, hym, stm), sc_dn(T1.x, hy0, st0));
+            const double fb = sc_flux(sc_up(qv.x, hy0, sv0), sc_dn(qv.y, hy1, sv1), sc_up(T1.x, hy0, st0), sc_dn(T1.y, hy1, st1));
+            const double fc = lane_dn1(fa);
+            const double rx = rm[1], sxW = rm[2], sxE = rm[3];
+            double cn[2], rr[2];
+#pragma unroll
+            for (int e = 0; e < 2; e++) {
+                const double tc = e ? T1.y : T1.x, tW = e ? T0.y : T0.x, tE = e ? T2.y : T2.x;
+                const double tS = e ? T1.x : tm, tN = e ? tp : T1.y;
+                const double ry = e ? ry1 : ry0, syS = e ? rs1 : rs0, syN = e ? rs2 : rs1;
+                const double D0 = hpe * (tc - tW) * sxW, D1 = hpe * (tE - tc) * sxE;
+                const double D2 = hpe * (tc - tS) * syS, D3 = hpe * (tN - tc) * syN;
+                sc_finish(tc, e ? c0v.y : c0v.x, D0, D1, D2, D3, e ? FW.y : FW.x, e ? FE.y : FE.x, e ? fb : fa,
+                          e ? fc : fb, rx, ry, dt, cn[e], rr[e]);
+            }
+            const int m = r - 2;
+            const bool live = m >= ib && m < ie && m >= A.ilo && m < A.ihi;
+            if (live && wr && m >= g.sr0 && m < g.sr1) acc0 += rr[0] * rr[0] + rr[1] * rr[1];
+            const unsigned off = (live && wr) ? ((unsigned)m * (unsigned)ld + (unsigned)c0) * 8u : OOB;
+            auto st2 = [&](__amdgpu_buffer_rsrc_t rs, const double* o) {
+                const nsu4 d = {(unsigned)__double2loint(o[0]), (unsigned)__double2hiint(o[0]),
+                                (unsigned)__double2loint(o[1]), (unsigned)__double2hiint(o[1])};
+                __builtin_amdgcn_raw_buffer_store_b128(d, rs, (int)off, 0, NT ? 2 : 0);
+            };
+            st2(bcq, cn);
+            st2(brq, rr);
+            FW = FE;
+            SPu = SCu; SPt = SCt;
+        };
+        // rows ib-2 .. ie+1 (the first two steps only fill the windows; row ib-1's slope needs ib)
+        const int r0 = ib - 2, r1 = ie + 1;
+#pragma unroll
+        for (int q = 0; q < SK; q++) {
+            load(r0 + q, QU[q], QT[q], QV[q], QC[q]);
+            asm volatile("" ::: "memory");
+        }
+        for (int r = r0; r <= r1; r += SK) {
+#pragma unroll
+            for (int q = 0; q < SK; q++) {   // (rows past r1: computed, not stored)
+                step(QU[q], QT[q], QV[q], QC[q], r + q);
+                load(r + q + SK, QU[q], QT[q], QV[q], QC[q]);
+            }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc0 += __shfl_xor(acc0, off, 64);
+    if (lane == 0 && w < nstr) A.part[wid] = acc0;
+}
+
+// (min, -max) of a plane's own cells per block: the scalar's monitor
+__global__ __launch_bounds__(256) void k_minmax(Geo g, const double* __restrict__ f, double* __restrict__ part, int rows) {
+    const int j = blockIdx.x * 64 + threadIdx.x;
+    const int lend = min((int)(blockIdx.y + 1) * 4 * rows, g.nxl);
+    double acc[2] = {INFINITY, INFINITY};
+    for (int li = blockIdx.y * 4 * rows + threadIdx.y; li < lend && j < g.ny; li += 4) {
+        const double x = f[(ptrdiff_t)li * g.ld + j];
+        acc[0] = fmin(acc[0], x != x ? -INFINITY : x);
+        acc[1] = fmin(acc[1], x != x ? -INFINITY : -x);
+    }
+    block_reduce_min<2>(acc, part + 2 * (blockIdx.x + gridDim.x * blockIdx.y));
+}
 
 // ------------------------------------------------ K3 / K5 as streaming strips
 // The same strip walk as k_sweep (128 loaded columns, 124 written, 2 per lane, x-neighbours
@@ -4902,15 +5269,8 @@ int launch_rhs(const Knobs& kn, const Geo& g, const Coef& c, double dt, double r
         }
         const bool inner = A.jhi > 2 && A.ihi > A.ilo;
         if (!inner) A.P.nrun = 0;
-        RhsRingArgs& R = A.R;
-        R.jhi = A.jhi;
-        for (int li = 0; li < g.nxl; li++)
-            if ((li < A.ilo || li >= A.ihi) && R.nfull < 4) R.fr[R.nfull++] = li;
-        R.rlo = A.ilo;
-        R.rhi = A.ihi;
-        R.ncol = A.jhi <= 2 ? g.ny : 2 + (g.ny - A.jhi);   // (tiny grids: whole rows)
-        R.n = R.nfull * g.ny + (R.rhi - R.rlo) * R.ncol;
-        const int nring = (R.n + 255) / 256;
+        A.R.plan(g.nxl, g.ny, A.ilo, A.ihi, A.jhi);
+        const int nring = (A.R.n + 255) / 256;
         // the ring reads phi's and u, v's ghost rows (wall terms, MUSCL): with the edge phase
         A.nring = g_phase != 1 ? nring : 0;
         A.nsblk = (A.nsj * A.P.nrun + 3) / 4;
@@ -4946,6 +5306,50 @@ int launch_rhs(const Knobs& kn, const Geo& g, const Coef& c, double dt, double r
     const dim3 cg = cell_grid(g, rows);
     if (g_phase != 1)
         NS_LAUNCH(k_rhs<TopoRect>, cg, dim3(64, 4), 0, st, g, c, dt, re, u, v, phi, cu, cv, ru, rv, part, rows);
+    return (int)(cg.x * cg.y);
+}
+
+int launch_rhs_t(const Knobs& kn, const Geo& g, const Coef& c, const int* tneu, const double* tc, double dt, double pe,
+                 const double* u, const double* v, const double* q, double* cq, double* rq, double* part,
+                 hipStream_t st) {
+    if (g.fc || g_phase != 0 || g.nxl != g.nx) return -1;   // (one rank's rectangle: ns_scalar_enable refuses the rest)
+    ScalarBC B{};
+    for (int k = 0; k < 4; k++) { B.neu[k] = tneu[k]; B.c[k] = tc[k]; }
+    if (kn.cell_grid) {   // NSGPU_CELL=grid: thread per cell
+        const int rows = cell_rows(g);
+        const dim3 cg = cell_grid(g, rows);
+        NS_LAUNCH(k_rhs_t_grid, cg, dim3(64, 4), 0, st, g, c, B, dt, pe, u, v, q, cq, rq, part, rows);
+        return (int)(cg.x * cg.y);
+    }
+    RhsTArgs A{};
+    A.g = g; A.c = c; A.B = B; A.dt = dt; A.pe = pe; A.u = u; A.v = v; A.q = q; A.cq = cq; A.rq = rq; A.part = part;
+    // the strips' cells and the ring: K1's split (launch_rhs)
+    A.jhi = std::max(2, (g.ny - 2) & ~1);
+    A.ilo = std::max(0, std::min(2 - g.i0, g.nxl));
+    A.ihi = std::max(A.ilo, std::min(g.nx - 2 - g.i0, g.nxl));
+    A.nsj = (g.ny + SW - 1) / SW;
+    const void* kk = (const void*)k_rhs_t<true, RHS_T_SK>;
+    {
+        // the fewest rows that keep every strip in one resident round, as K1's
+        const long nsi = std::max(1L, resident_waves(kn, kk) / A.nsj);
+        const int L = std::min(std::max((int)((g.nxl + nsi - 1) / nsi + 1) & ~1, 8), K1_LMAX);
+        A.nstr = A.nsj * plan_rows(g.nxl, L, 2, &A.P);   // u, T rows ib-2 .. ie+1
+    }
+    const bool inner = A.jhi > 2 && A.ihi > A.ilo;
+    if (!inner) A.P.nrun = 0;
+    A.R.plan(g.nxl, g.ny, A.ilo, A.ihi, A.jhi);
+    A.nring = (A.R.n + 255) / 256;
+    A.nsblk = (A.nsj * A.P.nrun + 3) / 4;
+    if (!inner) (void)hipMemsetAsync(part, 0, sizeof(double) * A.nstr, st);   // (no inner cells: zero partials)
+    void* args[] = {&A};
+    if (launch_raw(kk, dim3(A.nsblk + A.nring), dim3(256), args, 0, st) != hipSuccess) return -1;
+    return A.nstr + A.nring;
+}
+
+int launch_minmax(const Geo& g, const double* f, double* part, hipStream_t st) {
+    const int rows = cell_rows(g);
+    const dim3 cg = cell_grid(g, rows);
+    NS_LAUNCH(k_minmax, cg, dim3(64, 4), 0, st, g, f, part, rows);
     return (int)(cg.x * cg.y);
 }
 

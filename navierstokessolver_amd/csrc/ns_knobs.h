@@ -19,7 +19,7 @@ struct Knobs {
     int rhs = RHS_STREAM;      // NSGPU_RHS: K1 as k_rhs_s strips (unset), =global the global-load k_rhs, any other value (lds) k_rhs_lds + k_rhs_bc
     int k1s = 0;               // NSGPU_K1S=3 / 24 / 32 / 33: the streaming K1's builds (waves, rows in flight, hy tables in SGPRs)
     int k1_l = 0;              // NSGPU_K1_L=n (>= 4): K1's rows per strip (0: one resident round)
-    int cell_grid = 0;         // NSGPU_CELL=grid: the thread-per-cell K3 / K5 / apply instead of the k_cell_s strips
+    int cell_grid = 0;         // NSGPU_CELL=grid: the thread-per-cell K3 / K5 / apply instead of the k_cell_s strips (and k_rhs_t_grid for k_rhs_t)
     int mask_cell = 1;         // NSGPU_MASK_CELL=0: a masked domain's K3 / K5 as thread-per-cell k_div / k_correct<TopoMask>
     int apply_grid = 0;        // NSGPU_APPLY=grid: the Poisson operator by k_apply only
     int sd3 = 0;               // NSGPU_SD3=2 / 3: rows in flight of the residual 3-sweep pass (0: 2 for two fields, 3 for one)

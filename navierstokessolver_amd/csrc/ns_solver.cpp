@@ -350,6 +350,30 @@ struct ns_solver {
     // of 40 B/cell less); any other entry point that reads or writes the fields runs K5 first (materialize)
     bool k5_defer_ok = false;    // one rank, rectangle, no NEUMANN side, the direct solve, hy uniform, streaming K1
     int corr_pend = 0, defer_now = 0, corr_k1 = 0;   // corr_k1: this step's K1 applied a deferred correction
+    // a rectangle's edge on each side (W, E, S, N) and the grid's edge count: ns_scalar_enable's bc[k] is per edge
+    int side_edge[4] = {-1, -1, -1, -1}, n_edges = 0;
+    double inv_h2 = 0.0;         // 1 / min(hx)^2 + 1 / min(hy)^2 (the Helmholtz SOR weights)
+    // the passive scalar (ns_scalar_enable; DESIGN.md 4 "Passive scalar"): nothing below exists without one.
+    // Planes laid out like the fields: T, its sweep partner, rT, cT0; its ghosts per side (q_g = neu ? q : -q + c);
+    // ct: the coefficient tables with the scalar's Dirichlet sides in bx / by (the sweeps' operator I - dt/(2 pe)
+    // L_T); partials, device slots and their pinned mirror of its own, so that a step's other reductions see
+    // exactly what they see without a scalar
+    struct Scalar {
+        enum { BN2 = 0, RES2, TMIN, NTMAX, AUX, NSLOT = 8 };   // device slots
+        bool on = false;
+        double pe = 0.0, omega = 1.0;
+        int neu[4] = {0, 0, 0, 0};
+        double c[4] = {0, 0, 0, 0};
+        double *mem = nullptr, *T = nullptr, *TT = nullptr, *R = nullptr, *C = nullptr;
+        double* bxy = nullptr;
+        nsg::Coef ct{};
+        double *part = nullptr, *scal = nullptr, *hs = nullptr;
+        hipEvent_t ev = nullptr, kev[2] = {nullptr, nullptr};
+        // the step's first batch of sweeps is what the previous step needed; it is enqueued, with its residual and
+        // the min / max of its result, before the velocities' Helmholtz solve, whose residual check brings them
+        int next = 4, ok_steps = 0, sweeps = 0, timed = 0;
+        ns_scalar_stats last{};
+    } sc;
 };
 
 namespace {
@@ -3516,6 +3540,95 @@ int materialize(ns_solver* s) {
     return correct(s);
 }
 
+// ---------------- the passive scalar (ns_scalar_enable): rT, then (I - dt/(2 pe) L_T) T^{n+1} = rT
+// the right-hand side from u^n, v^n, T^n, cT0 (k_rhs_t): cT0 <- cT in place, rT, ||rT||^2 -> its BN2 slot
+int scalar_rhs(ns_solver* s) {
+    auto& q = s->sc;
+    q.timed = 0;
+    if (s->timing && s->in_step) {
+        for (auto& e : q.kev)
+            if (!e) HIPCHK(hipEventCreate(&e));
+        CHK(t_begin(s, q.kev[0], q.kev[1]));
+    }
+    const int nb = nsg::launch_rhs_t(s->k, s->g, s->c, q.neu, q.c, s->dt, q.pe, s->arr[NS_ARR_U], s->arr[NS_ARR_V], q.T,
+                                     q.C, q.R, q.part, s->st);
+    if (nb < 0) { set_err("the scalar's right-hand side: launch refused"); return NS_EHIP; }
+    if (s->timing && s->in_step) {
+        CHK(t_end(s, q.kev[0], q.kev[1]));
+        q.timed = 1;
+    }
+    nsg::launch_reduce_sum(q.part, nb, 1, q.scal + ns_solver::Scalar::BN2, s->st);
+    return 0;
+}
+
+// n (even) red-black SOR sweeps of T as two-sweep passes, the last with its output's residual; then the residual
+// and the min / max of the result on their way to the host (no wait: scalar_wait)
+int scalar_batch(ns_solver* s, int n) {
+    using S = ns_solver::Scalar;
+    auto& q = s->sc;
+    const double alpha = s->dt / (2 * q.pe);
+    int nb = 0;
+    for (int k = 0; k < n; k += 2) {
+        nb = nsg::launch_helm_sweep2(s->k, s->g, q.ct, alpha, q.omega, q.T, nullptr, q.TT, nullptr, q.R, nullptr,
+                                     k + 2 >= n ? q.part : nullptr, s->st, 1);
+        if (nb < 0) { set_err("the scalar's Helmholtz pass: launch refused"); return NS_EHIP; }
+        std::swap(q.T, q.TT);
+    }
+    q.sweeps += n;
+    double* pm = q.part + 2 * (size_t)nsg::max_partials(s->g);
+    const int nm = nsg::launch_minmax(s->g, q.T, pm, s->st);
+    nsg::launch_reduce_sum_min(q.part, nb, 1, q.scal + S::RES2, pm, nm, 2, q.scal + S::TMIN, s->st);
+    HIPCHK(hipMemcpyAsync(q.hs, q.scal, S::NSLOT * sizeof(double), hipMemcpyDeviceToHost, s->st));
+    HIPCHK(hipEventRecord(q.ev, s->st));
+    return 0;
+}
+
+// wait for the batch in flight and run further ones (twice the sweeps so far each) until the residual is below
+// rtol ||rT||; the stats of the solve
+int scalar_wait(ns_solver* s) {
+    using S = ns_solver::Scalar;
+    auto& q = s->sc;
+    const double tol2 = s->rtol * s->rtol;
+    const int first = q.sweeps;
+    for (;;) {
+        HIPCHK(hipEventSynchronize(q.ev));
+        const double r2 = q.hs[S::RES2], b2 = q.hs[S::BN2];
+        if (!std::isfinite(r2)) { set_err("the scalar's Helmholtz residual is not finite"); return NS_EDIVERGE; }
+        q.last.res_t = b2 > 0 ? std::sqrt(r2 / b2) : std::sqrt(r2);
+        if (r2 <= tol2 * b2 || r2 == 0.0 || q.sweeps >= s->max_iters) break;
+        CHK(scalar_batch(s, std::max(2, std::min(q.sweeps, s->max_iters - q.sweeps + 1) & ~1)));
+    }
+    q.last.it_t = q.sweeps;
+    q.last.tmin = q.hs[S::TMIN];
+    q.last.tmax = -q.hs[S::NTMAX];
+    // the next solve's first batch: what this one needed; two fewer after four solves in a row whose first sufficed
+    if (q.sweeps > first) { q.next = q.sweeps; q.ok_steps = 0; }
+    else if (++q.ok_steps >= 4) { q.next = std::max(2, q.next - 2); q.ok_steps = 0; }
+    return 0;
+}
+
+// inside a step, after K1 (U, V = u^n, v^n in the deferred-K5 path too): the right-hand side and the first batch
+int scalar_begin(ns_solver* s) {
+    CHK(scalar_rhs(s));
+    s->sc.sweeps = 0;
+    return scalar_batch(s, s->sc.next);
+}
+// ... and after the velocities' Helmholtz solve, whose last residual check waited for the stream
+int scalar_end(ns_solver* s) {
+    auto& q = s->sc;
+    CHK(scalar_wait(s));
+    q.last.t_rhs_kernel_ms = 0.0;
+    q.last.n_rhs_kernels = 0;
+    if (q.timed) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, q.kev[0], q.kev[1]) == hipSuccess) {
+            q.last.t_rhs_kernel_ms = ms;
+            q.last.n_rhs_kernels = 1;
+        }
+    }
+    return 0;
+}
+
 int check_arr(ns_solver* s, int which) {
     if (!s) { set_err("null solver"); return NS_EINVAL; }
     if (which < 0 || which >= NS_NUM_ARR) { set_err("bad array index %d", which); return NS_EINVAL; }
@@ -3719,6 +3832,7 @@ int host_geometry(ns_solver* s, const ns_grid_desc* gd, const ns_params* p, Host
     s->rank = p->rank;
     s->nranks = p->nranks;
     s->ncells = (double)gd->nx * gd->ny;
+    s->n_edges = gd->n_edges;
     // (the widest exchange is the residual 3-sweep pass's 7 rows = HALO, fed from one neighbour; a slab too thin
     // for an overlapped pass to have an interior runs the pass whole after its exchange, plan_rows -- slabs of 10
     // to 13 rows take the 3-sweep passes: test_thin_slabs_take_three_sweep_passes)
@@ -3747,6 +3861,7 @@ int host_geometry(ns_solver* s, const ns_grid_desc* gd, const ns_params* p, Host
         }
         for (int k = 0; k < 4; k++) {
             if (side_edge[k] < 0) { set_err("side %d has no edge: not a rectangle", k); return NS_EINVAL; }
+            s->side_edge[k] = side_edge[k];
             nsg::EdgeDev D;
             if (int rc = edge_dev(gd, p, side_edge[k], &D)) return rc;
             g.enx[k] = D.enx;
@@ -3796,6 +3911,7 @@ void take_params(ns_solver* s, const ns_grid_desc* gd, const ns_params* p) {
         // optimal SOR omega = 2 / (1 + sqrt(1 - rho^2))
         const double a = p->dt / (2 * p->re);
         const double hxm = *std::min_element(gd->hx, gd->hx + gd->nx), hym = *std::min_element(gd->hy, gd->hy + gd->ny);
+        s->inv_h2 = 1 / (hxm * hxm) + 1 / (hym * hym);
         const double t = 2 * a * (1 / (hxm * hxm) + 1 / (hym * hym));
         const double rho = t / (1 + t);
         s->omega_v = p->omega_v > 0 ? p->omega_v : 2.0 / (1.0 + std::sqrt(1.0 - rho * rho));
@@ -4225,10 +4341,24 @@ int ns_create(const ns_grid_desc* gd, const ns_params* p, ns_solver** out) {
     return 0;
 }
 
+static void scalar_free(ns_solver* s) {
+    auto& q = s->sc;
+    if (q.mem) (void)hipFree(q.mem);
+    if (q.bxy) (void)hipFree(q.bxy);
+    if (q.part) (void)hipFree(q.part);
+    if (q.scal) (void)hipFree(q.scal);
+    if (q.hs) (void)hipHostFree(q.hs);
+    if (q.ev) (void)hipEventDestroy(q.ev);
+    for (auto e : q.kev)
+        if (e) (void)hipEventDestroy(e);
+    q = ns_solver::Scalar{};
+}
+
 void ns_destroy(ns_solver* s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
     if (s->st) (void)hipStreamSynchronize(s->st);
+    scalar_free(s);
     if (s->comm) (void)ncclCommDestroy(s->comm);
     if (s->mev) (void)hipEventDestroy(s->mev);
     if (s->mm_host) (void)hipHostFree(s->mm_host);
@@ -4294,6 +4424,9 @@ static int step_body(ns_solver* s, ns_stats& st) {
 
 static int step_body_(ns_solver* s, ns_stats& st) {
     CHK(rhs(s, true));                                             // ConstructRHS_V       (:546)
+    // the passive scalar sees u^n, v^n as K1 does (which wrote them in the deferred-K5 path): its right-hand side
+    // and first batch of sweeps here, their residual read after the velocities' Helmholtz check
+    if (s->sc.on) CHK(scalar_begin(s));
     // Helmholtz initial guess: u^n.  (The previous step's u* -- kept by correct() in TMPU/TMPV --
     // was measured worse during the cavity's start-up transient: 14.7 vs 11 sweeps/step at 4096^2.)
     // rhs ghost rows (a checked pair pass and the 3-sweep pass read ib-5): multi-rank passes take them with
@@ -4306,6 +4439,7 @@ static int step_body_(ns_solver* s, ns_stats& st) {
     s->extrap_pending = s->phim ? 1 : 0;
     CHK(helm_solve(s, &st.it_u, &st.res_u, &st.res_v));            // KSPSolve(uSolver) x2 (:547-548)
     if (s->extrap_pending) { s->extrap_pending = 0; CHK(extrapolate_phi(s)); }
+    if (s->sc.on) CHK(scalar_end(s));
     st.it_v = st.it_u;
     for (int k = 0; k < s->hn; k++) {   // (helm_solve's last residual check synchronised the stream)
         float ms = 0.f;
@@ -4692,6 +4826,138 @@ int ns_kernel(ns_solver* s, int which, int iters, double* out) {
         set_err("unknown kernel %d", which);
         return NS_EINVAL;
     }
+}
+
+// ---- passive scalar
+static int scalar_check(ns_solver* s, const char* who) {
+    if (!s) { set_err("null solver"); return NS_EINVAL; }
+    if (!s->sc.on) { set_err("%s: no scalar enabled (ns_scalar_enable)", who); return NS_EINVAL; }
+    HIPCHK(hipSetDevice(s->device));
+    nsg::set_compute_cus(s->compute_cus);
+    return 0;
+}
+
+int ns_scalar_enable(ns_solver* s, const ns_scalar_desc* d) {
+    if (!s || !d) { set_err("null argument"); return NS_EINVAL; }
+    if (s->sc.on) { set_err("ns_scalar_enable: the solver already carries a scalar"); return NS_EINVAL; }
+    if (s->g.fc) { set_err("ns_scalar_enable: a masked polygon (cell_id != NULL) is not supported"); return NS_EINVAL; }
+    if (s->nranks > 1) { set_err("ns_scalar_enable: nranks > 1 is not supported"); return NS_EINVAL; }
+    if (!(d->pe > 0)) { set_err("ns_scalar_enable: Peclet number should be positive"); return NS_EINVAL; }
+    if (d->n_edges != s->n_edges || !d->bc) {
+        set_err("ns_scalar_enable: %d boundary conditions for a grid of %d edges", d->bc ? d->n_edges : 0, s->n_edges);
+        return NS_EINVAL;
+    }
+    for (int e = 0; e < d->n_edges; e++)
+        if (d->bc[e].type != NS_SBC_DIRICHLET && d->bc[e].type != NS_SBC_ZEROGRAD) {
+            set_err("ns_scalar_enable: edge %d: unknown scalar boundary type %d", e, d->bc[e].type);
+            return NS_EINVAL;
+        }
+    HIPCHK(hipSetDevice(s->device));
+    auto& q = s->sc;
+    const nsg::Geo& g = s->g;
+    q.pe = d->pe;
+    for (int k = 0; k < 4; k++) {
+        const ns_scalar_bc& b = d->bc[s->side_edge[k]];
+        q.neu[k] = b.type == NS_SBC_ZEROGRAD;
+        q.c[k] = q.neu[k] ? 0.0 : 2 * b.value;
+    }
+    {   // the sweeps' SOR weight, as omega_v with pe in re's place (take_params)
+        const double t = s->dt / q.pe * s->inv_h2, rho = t / (1 + t);
+        q.omega = 2.0 / (1.0 + std::sqrt(1.0 - rho * rho));
+    }
+    // the Helmholtz tables' Dirichlet-face terms 2 / h^2 on the scalar's Dirichlet sides (coef_tables' bx / by)
+    std::vector<double> hx(g.nx), hy(g.ny), bxy((size_t)g.nx + g.ny, 0.0);
+    HIPCHK(hipMemcpy(hx.data(), s->c.hx, g.nx * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(hy.data(), s->c.hy, g.ny * sizeof(double), hipMemcpyDeviceToHost));
+    if (!q.neu[0]) bxy[0] += 2.0 / (hx[0] * hx[0]);
+    if (!q.neu[1]) bxy[g.nx - 1] += 2.0 / (hx[g.nx - 1] * hx[g.nx - 1]);
+    if (!q.neu[2]) bxy[g.nx] += 2.0 / (hy[0] * hy[0]);
+    if (!q.neu[3]) bxy[g.nx + g.ny - 1] += 2.0 / (hy[g.ny - 1] * hy[g.ny - 1]);
+    const int np = nsg::max_partials(g);
+    int rc = dev_upload(s, &q.bxy, bxy, "scalar tables");
+    if (!rc) rc = dev_alloc(s, &q.mem, 4 * s->plane * sizeof(double), true, "scalar planes");
+    if (!rc) rc = dev_alloc(s, &q.part, (size_t)np * 8 * sizeof(double), false, "scalar partials");
+    if (!rc) rc = dev_alloc(s, &q.scal, ns_solver::Scalar::NSLOT * sizeof(double), true, "scalar slots");
+    if (!rc && hipHostMalloc(&q.hs, ns_solver::Scalar::NSLOT * sizeof(double), hipHostMallocDefault) != hipSuccess) {
+        set_err("hipHostMalloc failed");
+        rc = NS_ENOMEM;
+    }
+    if (!rc && hipEventCreateWithFlags(&q.ev, hipEventDisableTiming) != hipSuccess) { set_err("event create failed"); rc = NS_EHIP; }
+    if (!rc && hipStreamSynchronize(s->st) != hipSuccess) { set_err("stream sync failed"); rc = NS_EHIP; }
+    if (rc) {
+        scalar_free(s);
+        return rc;
+    }
+    double* p0 = q.mem + (size_t)s->hp * g.ld;
+    q.T = p0; q.TT = p0 + s->plane; q.R = p0 + 2 * s->plane; q.C = p0 + 3 * s->plane;
+    q.ct = s->c;
+    q.ct.bx = q.bxy;
+    q.ct.by = q.bxy + g.nx;
+    q.on = true;
+    return 0;
+}
+
+static int scalar_copy(ns_solver* s, double* plane, double* out, const double* in) {
+    const size_t w = (size_t)s->g.ny * 8, ldb = (size_t)s->g.ld * 8;
+    if (out) HIPCHK(hipMemcpy2DAsync(out, w, plane, ldb, w, s->g.nxl, hipMemcpyDeviceToHost, s->st));
+    if (in) HIPCHK(hipMemcpy2DAsync(plane, ldb, in, w, w, s->g.nxl, hipMemcpyHostToDevice, s->st));
+    return 0;
+}
+
+int ns_scalar_set(ns_solver* s, const double* T, const double* cT0) {
+    CHK(scalar_check(s, "ns_scalar_set"));
+    if (T) CHK(scalar_copy(s, s->sc.T, nullptr, T));
+    if (cT0) CHK(scalar_copy(s, s->sc.C, nullptr, cT0));
+    HIPCHK(hipStreamSynchronize(s->st));
+    return 0;
+}
+
+int ns_scalar_get(ns_solver* s, double* T, double* cT0) {
+    CHK(scalar_check(s, "ns_scalar_get"));
+    if (T) CHK(scalar_copy(s, s->sc.T, T, nullptr));
+    if (cT0) CHK(scalar_copy(s, s->sc.C, cT0, nullptr));
+    HIPCHK(hipStreamSynchronize(s->st));
+    return 0;
+}
+
+int ns_scalar_get_rhs(ns_solver* s, double* rT) {
+    CHK(scalar_check(s, "ns_scalar_get_rhs"));
+    if (rT) CHK(scalar_copy(s, s->sc.R, rT, nullptr));
+    HIPCHK(hipStreamSynchronize(s->st));
+    return 0;
+}
+
+int ns_scalar_last(ns_solver* s, ns_scalar_stats* out) {
+    CHK(scalar_check(s, "ns_scalar_last"));
+    if (out) *out = s->sc.last;
+    return 0;
+}
+
+int ns_scalar_kernel(ns_solver* s, int which, double* out) {
+    using S = ns_solver::Scalar;
+    CHK(scalar_check(s, "ns_scalar_kernel"));
+    CHK(materialize(s));   // (a deferred correction first: U, V = u^n, v^n)
+    auto& q = s->sc;
+    if (which == 1) {
+        CHK(scalar_rhs(s));
+        HIPCHK(hipMemcpyAsync(q.hs, q.scal, S::NSLOT * sizeof(double), hipMemcpyDeviceToHost, s->st));
+        HIPCHK(hipStreamSynchronize(s->st));
+        if (out) out[0] = q.hs[S::BN2];
+        return 0;
+    }
+    if (which == 2) {
+        // ||rT||^2 of the plane as it stands, then batches from the current T
+        const int nb = nsg::launch_sums(s->g, q.R, q.part, s->st);
+        nsg::launch_reduce_sum(q.part, nb, 2, q.scal + S::AUX, s->st);
+        HIPCHK(hipMemcpyAsync(q.scal + S::BN2, q.scal + S::AUX + 1, sizeof(double), hipMemcpyDeviceToDevice, s->st));
+        q.sweeps = 0;
+        CHK(scalar_batch(s, q.next));
+        CHK(scalar_wait(s));
+        if (out) { out[0] = q.last.it_t; out[1] = q.last.res_t; }
+        return 0;
+    }
+    set_err("ns_scalar_kernel: unknown kernel %d", which);
+    return NS_EINVAL;
 }
 
 int ns_mg_transfer(ns_solver* s, int op, double* coarse) {

@@ -80,6 +80,7 @@ class GpuSolver:
                          ctypes.pointer(host_transport.struct) if host_transport is not None else None,
                          mg_omega)
         self._transport = host_transport  # keep the callbacks alive
+        self._scalar = False
         h = ctypes.c_void_p()
         L.check(L.lib().ns_create(ctypes.byref(desc), ctypes.byref(prm), ctypes.byref(h)))
         self._h = h
@@ -119,7 +120,11 @@ class GpuSolver:
     def step(self) -> dict:
         st = L.NsStats()
         L.check(L.lib().ns_step(self._h, ctypes.byref(st)))
-        return st.as_dict()
+        d = st.as_dict()
+        if self._scalar:
+            ss = self.scalar_stats()
+            d["tmin"], d["tmax"] = ss["tmin"], ss["tmax"]
+        return d
 
     def step_async(self) -> dict:
         """ns_step_async: one step without the closing host sync; umin..vmax are the previous
@@ -169,6 +174,50 @@ class GpuSolver:
             if a is not None and a.size != n:
                 raise ValueError(f"compact field of {a.size} values; this slab holds {n} cells")
         L.check(L.lib().ns_set_fields(self._h, *[None if a is None else _dptr(a) for a in keep]))
+
+    # ---- passive scalar (ns_scalar_*: one rank's rectangle)
+    def enable_scalar(self, pe: float, bc) -> None:
+        """A scalar T carried by the step, Peclet number pe.  bc: one ("dirichlet", value) or ("zerograd",)
+        per grid edge, in the grid's edge order (cavity.rectangle: W, N, E, S).  T = cT0 = 0 afterwards."""
+        kinds = {"dirichlet": L.NS_SBC_DIRICHLET, "zerograd": L.NS_SBC_ZEROGRAD}
+        rows = []
+        for b in bc:
+            if not b or b[0] not in kinds:
+                raise ValueError(f"scalar boundary condition {b!r}: ('dirichlet', value) or ('zerograd',)")
+            rows.append(L.NsScalarBc(kinds[b[0]], float(b[1]) if b[0] == "dirichlet" else 0.0))
+        arr = (L.NsScalarBc * len(rows))(*rows)
+        desc = L.NsScalarDesc(pe, len(rows), arr)
+        L.check(L.lib().ns_scalar_enable(self._h, ctypes.byref(desc)))
+        self._scalar = True
+
+    def scalar(self, cT0: bool = False):
+        """T as the nx x ny plane (with cT0=True: T and the previous step's convective term)."""
+        T = np.empty(self.shape, dtype=np.float64)
+        C = np.empty(self.shape, dtype=np.float64) if cT0 else None
+        L.check(L.lib().ns_scalar_get(self._h, _dptr(T), _dptr(C) if cT0 else None))
+        return (T, C) if cT0 else T
+
+    def set_scalar(self, T, cT0=None) -> None:
+        keep = [None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(self.shape))
+                for a in (T, cT0)]
+        L.check(L.lib().ns_scalar_set(self._h, *[None if a is None else _dptr(a) for a in keep]))
+
+    def scalar_stats(self) -> dict:
+        """The latest step's tmin, tmax, it_t, res_t, t_rhs_kernel_ms, n_rhs_kernels (ns_scalar_last)."""
+        st = L.NsScalarStats()
+        L.check(L.lib().ns_scalar_last(self._h, ctypes.byref(st)))
+        return st.as_dict()
+
+    def scalar_kernel(self, which: int) -> np.ndarray:
+        """ns_scalar_kernel (tests): 1 = the right-hand side alone, 2 = the converged solve of the current rT."""
+        out = np.zeros(2, dtype=np.float64)
+        L.check(L.lib().ns_scalar_kernel(self._h, which, _dptr(out)))
+        return out
+
+    def scalar_rhs(self) -> np.ndarray:
+        out = np.empty(self.shape, dtype=np.float64)
+        L.check(L.lib().ns_scalar_get_rhs(self._h, _dptr(out)))
+        return out
 
     def kernel(self, which: int, iters: int = 1) -> np.ndarray:
         out = np.zeros(8, dtype=np.float64)
