@@ -1591,6 +1591,180 @@ __global__ void __launch_bounds__(64) k_fps_mid(FpsArgs a, const double* __restr
     st2(a.gb + (size_t)(a.ngrp + grp) * a.ld + k0, GR[0], GR[1]);
 }
 
+// (r7) one rank: the forward group scan, k_fps_mid and the backward group scan in ONE launch -- three strictly serial
+// launches of a few workgroups each (5.4 + 12.3 + 5.4 us at 4096^2, and two launch boundaries).  A workgroup owns
+// MS_MB modes: it scans their group aggregates forward (ga -> the carries gc, kept in the LDS), forms every chunk's
+// ya and cb from them as k_fps_mid does (one thread per group and mode pair, the same fma sequence) with the groups'
+// backward aggregates (BX, BR: gb) kept in the LDS too, and scans those backward into gx.  Both scans are
+// k_fps_scan_seg's for ngrp >= 2 S (the same segments, the same fma chains) and k_fps_scan's below that, with a zero
+// carry-in (one rank): ya, cb and gx come out as the three launches leave them, bit for bit.
+constexpr int MS_MB = 16;     // modes per workgroup (a 128-byte line of every table row)
+constexpr int MS_NT = 512;    // threads: MS_MB x S lanes scan, all of them take the (group, mode pair) tasks
+// one direction's scan of ngrp (E, P) pairs per mode: ldE / ldP(grp, lane) -> stC(grp, lane, carry-in)
+template <int S, bool BACK, class LE, class LP, class SC>
+__device__ __forceinline__ void ms_scan(int ngrp, int ny, int kb, int tid, LE ldE, LP ldP, SC stC, double (*sE)[MS_MB],
+                                        double (*sP)[MS_MB], double (*sY)[MS_MB]) {
+    const int lane = tid % MS_MB, s = tid / MS_MB;
+    const int k = kb + lane;
+    constexpr int B = 8;
+    auto gq = [&](int q) { return BACK ? ngrp - 1 - q : q; };
+    if (S > 1 && ngrp >= 2 * S) {   // (k_fps_scan_seg)
+        const bool act = s < S && k < ny;
+        const int per = (ngrp + S - 1) / S, q0 = s * per, q1 = min(ngrp, q0 + per);
+        double AE = 0.0, AP = 1.0;
+        if (act) {
+            for (int qb = q0; qb < q1; qb += B) {
+                double E[B], P[B];
+#pragma unroll
+                for (int t = 0; t < B; t++) {
+                    const int q = qb + t, qc = min(q, q1 - 1);
+                    const double e = ldE(gq(qc), lane), pv = ldP(gq(qc), lane);
+                    E[t] = q < q1 ? e : 0.0;
+                    P[t] = q < q1 ? pv : 1.0;
+                }
+#pragma unroll
+                for (int t = 0; t < B; t++) {
+                    AE = fma(P[t], AE, E[t]);
+                    AP = P[t] * AP;
+                }
+            }
+        }
+        if (s < S) {
+            sE[s][lane] = AE;
+            sP[s][lane] = AP;
+        }
+        __syncthreads();
+        if (s == 0 && k < ny) {
+            double Y = 0.0;
+            for (int t = 0; t < S; t++) {
+                sY[t][lane] = Y;
+                Y = fma(sP[t][lane], Y, sE[t][lane]);
+            }
+        }
+        __syncthreads();
+        if (act) {
+            double Y = sY[s][lane];
+            for (int qb = q0; qb < q1; qb += B) {
+                double E[B], P[B];
+#pragma unroll
+                for (int t = 0; t < B; t++) {
+                    const int q = qb + t, qc = min(q, q1 - 1);
+                    const double e = ldE(gq(qc), lane), pv = ldP(gq(qc), lane);
+                    E[t] = q < q1 ? e : 0.0;
+                    P[t] = q < q1 ? pv : 1.0;
+                }
+#pragma unroll
+                for (int t = 0; t < B; t++) {
+                    const int q = qb + t;
+                    if (q < q1) {
+                        stC(gq(q), lane, Y);
+                        Y = fma(P[t], Y, E[t]);
+                    }
+                }
+            }
+        }
+    } else if (s == 0 && k < ny) {   // (k_fps_scan)
+        double Y = 0.0;
+        for (int q0 = 0; q0 < ngrp; q0 += B) {
+            double E[B], P[B];
+#pragma unroll
+            for (int t = 0; t < B; t++) {
+                const int q = q0 + t, qc = min(q, ngrp - 1);
+                const double e = ldE(gq(qc), lane), pv = ldP(gq(qc), lane);
+                E[t] = q < ngrp ? e : 0.0;
+                P[t] = q < ngrp ? pv : 1.0;
+            }
+#pragma unroll
+            for (int t = 0; t < B; t++) {
+                const int q = q0 + t;
+                if (q < ngrp) {
+                    stC(gq(q), lane, Y);
+                    Y = fma(P[t], Y, E[t]);
+                }
+            }
+        }
+    }
+}
+template <int S>
+__global__ void __launch_bounds__(MS_NT) k_fps_midscan(FpsArgs a, const double* __restrict__ f) {
+    extern __shared__ double ms_lds[];   // gc | BX | BR of the workgroup's modes: ngrp x MS_MB each
+    __shared__ double sE[S][MS_MB], sP[S][MS_MB], sY[S][MS_MB];
+    static_assert(MS_NT >= S * MS_MB, "k_fps_midscan: a thread per mode and segment");
+    const int tid = threadIdx.x, ngrp = a.ngrp, ld = a.ld, kb = blockIdx.x * MS_MB;
+    double* gc = ms_lds;
+    double* gbx = gc + (size_t)ngrp * MS_MB;
+    double* gbr = gbx + (size_t)ngrp * MS_MB;
+    // forward: ga -> gc
+    ms_scan<S, false>(
+        ngrp, a.ny, kb, tid, [&](int grp, int lane) { return a.ga[(size_t)grp * ld + kb + lane]; },
+        [&](int grp, int lane) { return a.ga[(size_t)(ngrp + grp) * ld + kb + lane]; },
+        [&](int grp, int lane, double Y) { gc[grp * MS_MB + lane] = Y; }, sE, sP, sY);
+    __syncthreads();
+    // k_fps_mid's body per (group, mode pair)
+    constexpr int NP = MS_MB / 2;
+    for (int task = tid; task < NP * ngrp; task += MS_NT) {
+        const int pr = task % NP, grp = task / NP;
+        const int k0 = kb + 2 * pr;
+        if (k0 >= a.ny) continue;
+        if (a.outE && !a.s0_given && k0 == 0 && grp == 0) *a.s0 = mode0_shift(a, 0, f);   // (t2b overwrites the plane)
+        double Y[2] = {gc[grp * MS_MB + 2 * pr], gc[grp * MS_MB + 2 * pr + 1]};
+        double BX[FPS_G][2], BR[FPS_G][2];
+        double2 le[FPS_G], lp[FPS_G], lb[FPS_G], lbe[FPS_G], lbr[FPS_G];
+#pragma unroll
+        for (int w = 0; w < FPS_G; w++) {
+            const int c = min(grp * FPS_G + w, a.nch - 1);
+            le[w] = ld2(a.ca + (size_t)c * a.ld + k0);
+            lp[w] = ld2(a.ca + (size_t)(a.nch + c) * a.ld + k0);
+            lb[w] = ld2(a.cb + (size_t)c * a.ld + k0);
+            lbe[w] = ld2(a.bt + (size_t)c * a.ld + k0);
+            lbr[w] = ld2(a.bt + (size_t)(a.nch + c) * a.ld + k0);
+        }
+#pragma unroll
+        for (int w = 0; w < FPS_G; w++) {
+            const int c = grp * FPS_G + w;
+            BX[w][0] = BX[w][1] = 0.0;
+            BR[w][0] = BR[w][1] = 1.0;
+            if (c < a.nch) {
+                double2 e = le[w];
+                const double2 pp = lp[w];
+                double2 bl = lb[w];
+                if (a.m0e && k0 == 0) {   // (r5, the deferred mean: t1b's mode 0 saw b's raw coefficients)
+                    const double sft = a.ny * *a.m0s;
+                    e.x -= sft * a.m0e[c];
+                    bl.x -= sft * a.m0b[c];
+                }
+                const double2 be = lbe[w], br = lbr[w];
+                st2(a.ya + (size_t)c * a.ld + k0, Y[0], Y[1]);
+                BX[w][0] = fma(be.x, Y[0], bl.x);
+                BX[w][1] = fma(be.y, Y[1], bl.y);
+                BR[w][0] = br.x;
+                BR[w][1] = br.y;
+                st2(a.cb + (size_t)c * a.ld + k0, BX[w][0], BX[w][1]);
+                Y[0] = fma(pp.x, Y[0], e.x);
+                Y[1] = fma(pp.y, Y[1], e.y);
+            }
+        }
+        double GX[2] = {0.0, 0.0}, GR[2] = {1.0, 1.0};
+#pragma unroll
+        for (int w = FPS_G - 1; w >= 0; w--) {
+            GX[0] = fma(BR[w][0], GX[0], BX[w][0]);
+            GX[1] = fma(BR[w][1], GX[1], BX[w][1]);
+            GR[0] = BR[w][0] * GR[0];
+            GR[1] = BR[w][1] * GR[1];
+        }
+        gbx[grp * MS_MB + 2 * pr] = GX[0];
+        gbx[grp * MS_MB + 2 * pr + 1] = GX[1];
+        gbr[grp * MS_MB + 2 * pr] = GR[0];
+        gbr[grp * MS_MB + 2 * pr + 1] = GR[1];
+    }
+    __syncthreads();
+    // backward: (BX, BR) -> gx
+    ms_scan<S, true>(
+        ngrp, a.ny, kb, tid, [&](int grp, int lane) { return gbx[grp * MS_MB + lane]; },
+        [&](int grp, int lane) { return gbr[grp * MS_MB + lane]; },
+        [&](int grp, int lane, double Y) { a.gx[(size_t)grp * ld + kb + lane] = Y; }, sE, sP, sY);
+}
+
 // T2b: the chunk's exact values -- the forward recurrence from its carry-in Y_in (ya), the back
 // substitution from its carry-in X_in (the group's, through the later chunks' (BX, BR)) -- in place
 // (GHOST: the deep slabs' variant with a.ghost's two extra rows -- a separate build, since keeping the carries live
@@ -2228,6 +2402,12 @@ void launch_fps_t1b(const FpsArgs& a, const double* f, hipStream_t st) {
 }
 void launch_fps_mid(const FpsArgs& a, const double* f, hipStream_t st) {
     hipLaunchKernelGGL(k_fps_mid, dim3((a.ny + 127) / 128, a.ngrp), dim3(64), 0, st, a, f);
+}
+bool launch_fps_midscan(const FpsArgs& a, const double* f, hipStream_t st) {
+    const size_t lds = 3 * (size_t)a.ngrp * MS_MB * sizeof(double);
+    if (!NS_TAILS || a.mid_local || lds > 48 * 1024 || a.ny % MS_MB != 0) return false;
+    hipLaunchKernelGGL(k_fps_midscan<FPS_SSEG>, dim3(a.ny / MS_MB), dim3(MS_NT), lds, st, a, f);
+    return true;
 }
 namespace {
 __global__ void k_fps_oe_s0(const double* __restrict__ f, int row, int ld, int last, double* __restrict__ out) {

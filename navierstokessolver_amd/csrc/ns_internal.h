@@ -7,6 +7,11 @@
 
 #include "ns_knobs.h"
 
+#ifndef NS_TAILS
+#define NS_TAILS 1   // (r7) 0: K1''s reduction and the direct solve's group scans keep their own launches (A/B: make
+                     // variant V=notails DEFS="-DNS_TAILS=0")
+#endif
+
 namespace nsg {
 
 constexpr int HALO = 7;  // ghost rows per side: K1's MUSCL stencil (2), the 2-sweep pass's cone (4),
@@ -190,6 +195,10 @@ void launch_reduce_min(const double* p, int n, int nv, double* out, hipStream_t 
 // Poisson prep: from sums (S, S2) and N -> shift = S/N, out[1] = S2 - S^2/N (= ||b||^2)
 // one rank: launch_reduce_sum (nv = 2) + launch_finish_mean in one launch
 void launch_reduce_sum_mean(const double* p, int n, double* sums, double ncells, double* out, hipStream_t st);
+// (r7) one launch for what the Helmholtz check's host read waits for: launch_reduce_sum_segs(pr, nr, 2, outr) and
+// launch_reduce_sum_min(ps, ns, 2, outs, pm, ns, 4, outm) (K1''s partials), four workgroups side by side
+void launch_reduce_step(const double* pr, int nr, double* outr, const double* ps, int ns, double* outs, const double* pm,
+                        double* outm, hipStream_t st);
 void launch_finish_mean(const double* sums, double ncells, double* shift_and_bn2, hipStream_t st);
 // multi-rank scalar bus: gathered = P rank slots of nv (<= 16) values; value t folded over the ranks in rank
 // order (a sum for t < nsum, a min after) -> out[dst[t]]
@@ -446,6 +455,9 @@ void launch_fps_t3(const FpsArgs& a, double* f, hipStream_t st);
 // backward aggregates per chunk), t2b (the exact values)
 void launch_fps_t1b(const FpsArgs& a, const double* f, hipStream_t st);
 void launch_fps_mid(const FpsArgs& a, const double* f, hipStream_t st);
+// (r7, one rank) the forward group scan, mid and the backward group scan in one launch: ya, cb and gx as the three
+// launches leave them, bit for bit (gc and gb stay in the workgroup); false: not taken (too many groups for the LDS)
+bool launch_fps_midscan(const FpsArgs& a, const double* f, hipStream_t st);
 void launch_fps_t2b(const FpsArgs& a, double* f, hipStream_t st);
 // (r6) slabs with an E outflow: out = 2 f'_{n-1} (mode 0 of the outflow row's eliminated coefficients) on the rank that
 // holds that row (last != 0), 0 on the others -- all-reduced (sum) into mode 0's projected shift

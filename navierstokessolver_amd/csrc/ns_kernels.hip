@@ -4496,6 +4496,19 @@ __global__ __launch_bounds__(1024) void k_reduce_sum_min(const double* __restric
     else reduce_min_body(pm, nm, nvm, outm, reinterpret_cast<double (*)[4]>(sh));
 }
 
+// (r7) one rank, the deferred correction: everything the Helmholtz check's host read waits for in ONE launch of four
+// workgroups side by side -- 0 / 1: the residual partials of u / v (k_reduce_sum_segs' two segments, each summed as
+// k_reduce_sum with nv = 1), 2: K1''s (||ru||^2, ||rv||^2) partials, 3: its four min / max partials (what
+// k_reduce_sum_min left behind K1').  K1''s results are read by the host only, so they can wait for this launch
+__global__ __launch_bounds__(1024) void k_reduce_step(const double* __restrict__ pr, int nr, double* __restrict__ outr,
+                                                      const double* __restrict__ ps, int ns, double* __restrict__ outs,
+                                                      const double* __restrict__ pm, double* __restrict__ outm) {
+    __shared__ double sh[1024];
+    if (blockIdx.x < 2) reduce_sum_body(pr + (size_t)blockIdx.x * nr, nr, 1, outr + blockIdx.x, sh);
+    else if (blockIdx.x == 2) reduce_sum_body(ps, ns, 2, outs, sh);
+    else reduce_min_body(pm, ns, 4, outm, reinterpret_cast<double (*)[4]>(sh));
+}
+
 // one rank: k_reduce_sum of the (sum, sum^2) partials and k_finish_mean in one launch (no
 // all-reduce between them; the same arithmetic in the same order)
 __global__ __launch_bounds__(1024) void k_reduce_sum_mean(const double* __restrict__ p, int n,
@@ -6482,6 +6495,10 @@ void launch_reduce_min(const double* p, int n, int nv, double* out, hipStream_t 
 void launch_reduce_sum_min(const double* ps, int ns, int nvs, double* outs, const double* pm, int nm, int nvm,
                            double* outm, hipStream_t st) {
     NS_LAUNCH(k_reduce_sum_min, dim3(2), dim3(1024), 0, st, ps, ns, nvs, outs, pm, nm, nvm, outm);
+}
+void launch_reduce_step(const double* pr, int nr, double* outr, const double* ps, int ns, double* outs, const double* pm,
+                        double* outm, hipStream_t st) {
+    NS_LAUNCH(k_reduce_step, dim3(4), dim3(1024), 0, st, pr, nr, outr, ps, ns, outs, pm, outm);
 }
 void launch_reduce_sum_mean(const double* p, int n, double* sums, double ncells, double* out, hipStream_t st) {
     NS_LAUNCH(k_reduce_sum_mean, dim3(1), dim3(1024), 0, st, p, n, sums, ncells, out);

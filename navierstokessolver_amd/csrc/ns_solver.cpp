@@ -176,6 +176,7 @@ struct ns_solver {
     int comm_cus = 0, compute_cus = 0;
     hipEvent_t xev[2] = {nullptr, nullptr};
     hipEvent_t fev = nullptr;     // fetch_begin / fetch_end: the scalars' copy to the host is done
+    int k1_red_nb = 0;            // (r7) K1''s partials wait for the Helmholtz check's reduction launch (their count)
     // ns_step_async: the step's min/max travel to mm_host behind the step's last kernel (mev);
     // read by the next ns_step_async (after that step's first host sync) or by ns_monitor
     double* mm_host = nullptr;
@@ -1122,7 +1123,14 @@ int helm_solve(ns_solver* s, int* its, double* resu, double* resv) {
         at += sweeps;
         sweeps += n;
         const bool ub = bus_on(s);
-        nsg::launch_reduce_sum_segs(s->part, nb, 2, s->scal + (ub ? S_RESL : S_RES), s->st);          // u, v
+        if (s->k1_red_nb > 0 && !ub) {
+            // (r7) with K1''s pending partials (rhs(): the deferred correction's path) in the same launch
+            nsg::launch_reduce_step(s->part, nb, s->scal + S_RES, s->part + 2 * (size_t)nsg::max_partials(s->g), s->k1_red_nb,
+                                    s->scal + S_HBN, s->part + 4 * (size_t)nsg::max_partials(s->g), s->scal + S_MM, s->st);
+            s->k1_red_nb = 0;
+        } else {
+            nsg::launch_reduce_sum_segs(s->part, nb, 2, s->scal + (ub ? S_RESL : S_RES), s->st);          // u, v
+        }
         if (first) nsg::launch_reduce_sum_segs(p0, nb0, 2, s->scal + (ub ? S_AUXL : S_AUX), s->st);
         static_assert(S_RES == S_HBN + 2, "the deferred RHS norms and the residuals in one all-reduce");
         if (ub) {
@@ -2386,10 +2394,15 @@ int pois_solve_fps(ns_solver* s, int* its, double* res, ns_stats* stt) {
         nsg::launch_fps_t3(fa, F, s->st);
     } else {
         nsg::launch_fps_t1b(fa1, F, s->st);
-        CHK(fps_scan(s, false));
-        s->mean_pend = false;
-        nsg::launch_fps_mid(fam, F, s->st);
-        CHK(fps_scan(s, true));
+        // (r7) one rank: the two group scans and k_fps_mid in one launch
+        if (s->nranks == 1 && nsg::launch_fps_midscan(fam, F, s->st)) {
+            s->mean_pend = false;
+        } else {
+            CHK(fps_scan(s, false));
+            s->mean_pend = false;
+            nsg::launch_fps_mid(fam, F, s->st);
+            CHK(fps_scan(s, true));
+        }
         nsg::FpsArgs fa2 = fa;
         fa2.ghost = s->deep && s->in_step ? 1 : 0;   // (r5: phi's ghost rows from the solve -- K5 exchanges none)
         nsg::launch_fps_t2b(fa2, F, s->st);
@@ -3429,8 +3442,11 @@ int rhs(ns_solver* s, bool defer_norm = false) {
         // (r6) the previous step's CorrectVelocities folded in: U, V hold u*, v*, PHI phi^n; the corrected u, v go to
         // the ping-pong partners (swapped below) and their min / max -- the previous step's monitor -- to S_MM
         double* mm = s->part + 4 * (size_t)nsg::max_partials(s->g);
+        // (r7) the ||RHS||^2 partials into the partial block's third quarter, which no launch before the Helmholtz
+        // check writes (the sweeps' residual partials take the first half): their reduction waits for that check's
+        double* ps = NS_TAILS ? s->part + 2 * (size_t)nsg::max_partials(s->g) : s->part;
         nb = nsg::launch_rhs(s->k, s->g, s->c, s->dt, s->re, s->arr[NS_ARR_U], s->arr[NS_ARR_V], s->arr[NS_ARR_PHI],
-                             s->arr[NS_ARR_CU], s->arr[NS_ARR_CV], s->arr[NS_ARR_RU], s->arr[NS_ARR_RV], s->part, s->st,
+                             s->arr[NS_ARR_CU], s->arr[NS_ARR_CV], s->arr[NS_ARR_RU], s->arr[NS_ARR_RV], ps, s->st,
                              2, s->arr[NS_ARR_TMPU], s->arr[NS_ARR_TMPV], mm);
         if (nb < 0) { set_err("K1 with the deferred correction: launch refused"); return NS_EHIP; }
         std::swap(s->arr[NS_ARR_U], s->arr[NS_ARR_TMPU]);
@@ -3441,7 +3457,10 @@ int rhs(ns_solver* s, bool defer_norm = false) {
         if (nb < 0) return nb;
         if (t) CHK(t_end(s, s->kev[0], s->kev[1]));
         // (the min / max and ||RHS||^2 partials in one launch; one rank: no bus, no all-reduce)
-        nsg::launch_reduce_sum_min(s->part, nb, 2, s->scal + S_HBN, mm, nb, 4, s->scal + S_MM, s->st);
+        // (r7) the host alone reads their results, after the Helmholtz pass: that check's reduction launch takes
+        // them along (helm_solve, launch_reduce_step) instead of a launch of their own on the chain behind K1'
+        if (NS_TAILS) s->k1_red_nb = nb;
+        else nsg::launch_reduce_sum_min(ps, nb, 2, s->scal + S_HBN, mm, nb, 4, s->scal + S_MM, s->st);
         return 0;
     } else {
         const HaloReq r[3] = {{&s->g, s->arr[NS_ARR_U], 2}, {&s->g, s->arr[NS_ARR_V], 2}, {&s->g, s->arr[NS_ARR_PHI], 1}};
