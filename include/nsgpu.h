@@ -278,7 +278,7 @@ int  ns_time_poisson_fp32(ns_solver* s, int warmup, int iters, double* out);
 /* ---- passive scalar (temperature / dye / concentration) carried by the time step ----
  * An optional field T advanced inside ns_step / ns_step_async by the velocities' scheme: AB2 on the MUSCL /
  * Rusanov convective term div(u T), Crank-Nicolson diffusion with the Peclet number pe in re's place, no
- * pressure term, no coupling back into momentum ("Passive scalar").  A solver without a scalar
+ * pressure term, no coupling back into momentum unless ns_scalar_buoyancy asks for it ("Passive scalar").  A solver without a scalar
  * runs exactly the launches it ran before.  Additive to ABI 9: no struct above changes, the scalar's planes
  * are allocated by ns_scalar_enable (not counted by ns_device_bytes).  One rank's rectangle only
  * (INTEGRATION.md 4): a masked polygon (cell_id != NULL) and nranks > 1 are refused. */
@@ -298,9 +298,22 @@ int  ns_scalar_set(ns_solver* s, const double* T, const double* cT0);    /* comp
 int  ns_scalar_get(ns_solver* s, double* T, double* cT0);
 int  ns_scalar_last(ns_solver* s, ns_scalar_stats* out);                 /* the latest completed step's */
 /* tests: which = 1 the right-hand side alone (cT0 <- cT, rT readable by ns_scalar_get_rhs; out[0] = ||rT||^2),
- * 2 = the converged solve of the current rT from the current T (out[0] = sweeps, out[1] = relative residual) */
+ * 2 = the converged solve of the current rT from the current T (out[0] = sweeps, out[1] = relative residual),
+ * 3 = the right-hand side with the buoyancy force (below) applied to the NS_ARR_RU / RV / CU / CV planes as they
+ *     stand (out[0] = ||rT||^2, out[1] = ||ru||^2, out[2] = ||rv||^2 of the planes after the call) */
 int  ns_scalar_kernel(ns_solver* s, int which, double* out);
 int  ns_scalar_get_rhs(ns_solver* s, double* rT);
+
+/* ---- Boussinesq buoyancy: the carried scalar drives the flow ----
+ * The body force f = (bx, by) (T - tref) in the momentum equation, AB2 in time like the convective term:
+ * dt (1.5 f^n - 0.5 f^{n-1}) joins RHS_u / RHS_v ("Buoyancy").  The force is folded into the stored
+ * explicit term: while buoyancy is on, NS_ARR_CU / NS_ARR_CV (and ns_set_fields' cu0 / cv0) hold the convective
+ * term MINUS the force, so a restart that carries them over carries the force history too.  Call after
+ * ns_scalar_enable, between steps; all-zero coefficients (the state after ns_scalar_enable) switch it off, and the
+ * step then runs exactly the launches of a passive scalar.  NS_EINVAL for a solver without a scalar, a NULL
+ * descriptor or a coefficient that is not finite.  Additive to ABI 9. */
+typedef struct ns_buoyancy_desc { double bx, by, tref; } ns_buoyancy_desc;   /* f = (bx, by) (T - tref) */
+int  ns_scalar_buoyancy(ns_solver* s, const ns_buoyancy_desc* d);
 
 /* ---- host-side helpers (no GPU needed) ---- */
 /* the x-slab [i0, i1) of `rank` out of `nranks` for nx cells */

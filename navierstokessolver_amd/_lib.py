@@ -100,6 +100,10 @@ class NsScalarStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class NsBuoyancyDesc(ctypes.Structure):
+    _fields_ = [("bx", ctypes.c_double), ("by", ctypes.c_double), ("tref", ctypes.c_double)]
+
+
 _P = ctypes.c_void_p
 _D = ctypes.POINTER(ctypes.c_double)
 SIGNATURES = {
@@ -125,6 +129,7 @@ SIGNATURES = {
     "ns_scalar_last": (ctypes.c_int, [_P, ctypes.POINTER(NsScalarStats)]),
     "ns_scalar_kernel": (ctypes.c_int, [_P, ctypes.c_int, _D]),
     "ns_scalar_get_rhs": (ctypes.c_int, [_P, _D]),
+    "ns_scalar_buoyancy": (ctypes.c_int, [_P, ctypes.POINTER(NsBuoyancyDesc)]),
     "ns_slab_range": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                      ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "ns_nccl_id_size": (ctypes.c_int, []),

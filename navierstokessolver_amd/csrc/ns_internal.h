@@ -100,9 +100,19 @@ int launch_rhs(const Knobs& kn, const Geo& g, const Coef& c, double dt, double r
 // the passive scalar's right-hand side (k_rhs_t; NSGPU_CELL=grid: k_rhs_t_grid, thread per cell): q = T, cq = cT0 ->
 // cT in place, rq = rT; tneu / tc: the scalar's ghost per side, q_g = tneu ? q : -q + tc; partials sum rT^2, one
 // per block (the count is returned).  One rank's rectangle only (-1 otherwise)
+// Boussinesq buoyancy, f = (bx, by) (q - tref): with a Buoy whose bx or by is not zero the buoyant variant
+// (k_rhs_t<.., FB> / k_rhs_t_grid<FB>) also rewrites K1's planes of each forced component in the same pass -- ru +=
+// 1.5 dt bx (q - tref), cu -= bx (q - tref), rv / cv with by likewise -- and writes the partials sum ru'^2 (then
+// sum rv'^2) to Buoy::part, one segment of the returned count per forced component, x first.  Neither forced
+// (or no Buoy): the plain kernel, no plane of Buoy's touched
+struct Buoy {
+    double bx, by, tref;
+    double *ru, *rv, *cu, *cv;
+    double* part;
+};
 int launch_rhs_t(const Knobs& kn, const Geo& g, const Coef& c, const int* tneu, const double* tc, double dt, double pe,
                  const double* u, const double* v, const double* q, double* cq, double* rq, double* part,
-                 hipStream_t st);
+                 hipStream_t st, const Buoy* by = nullptr);
 // (min, -max) partials of a plane's own cells, 2 per block (launch_reduce_min's layout)
 int launch_minmax(const Geo& g, const double* f, double* part, hipStream_t st);
 // K2: fused red-black SOR sweep of (I - a L_V) on u and v, (u,v) -> (uo,vo);

@@ -1969,6 +1969,56 @@ __device__ __forceinline__ double sc_wall(double r, double dt, double hpe, doubl
 #pragma clang fp contract(off)
     return r + dt * (hpe / (h * h)) * c;
 }
+// Boussinesq buoyancy ("Buoyancy"): the body force b (T - tref) of one component folded into K1's
+// right-hand side r and its stored explicit term e, which K1 carries from step to step with the AB2 weights:
+// r += 1.5 dt f, e -= f (e then holds convective-minus-force, so the next K1 adds 0.5 dt (c - f))
+__device__ __forceinline__ void sc_buoy(double b, double T, double tref, double dt, double& r, double& e) {
+#pragma clang fp contract(off)
+    const double f = b * (T - tref);
+    r = r + (1.5 * dt) * f;
+    e = e - f;
+}
+// the forced planes of k_rhs_t<.., FB> / k_rhs_t_grid<FB> (FB: bit 0 the x component, bit 1 the y component):
+// K1's RHS_u / RHS_v and cu / cv, rewritten in place, and the partials sum ru'^2 / rv'^2 (one per block, as part)
+struct BuoyDev {
+    double bx, by, tref;
+    double *ru, *rv, *cu, *cv;
+    double *pu, *pv;
+};
+// ... per cell, on the ring and in the thread-per-cell form: plane offset o, the cell's T
+template <int FB>
+__device__ __forceinline__ void buoy_cell(const BuoyDev& Y, double dt, ptrdiff_t o, double T, double* acc) {
+    if constexpr ((FB & 1) != 0) {
+        double r = Y.ru[o], e = Y.cu[o];
+        sc_buoy(Y.bx, T, Y.tref, dt, r, e);
+        Y.ru[o] = r;
+        Y.cu[o] = e;
+        acc[1] += r * r;
+    }
+    if constexpr ((FB & 2) != 0) {
+        double r = Y.rv[o], e = Y.cv[o];
+        sc_buoy(Y.by, T, Y.tref, dt, r, e);
+        Y.rv[o] = r;
+        Y.cv[o] = e;
+        acc[2] += r * r;
+    }
+}
+// a block's partials: rT^2, then the forced components' (a barrier between: block_reduce_sum's one LDS buffer)
+template <int FB, int N>
+__device__ __forceinline__ void buoy_partials(const BuoyDev& Y, double (&acc)[N], double* part, int blk) {
+    double a[1] = {acc[0]};
+    block_reduce_sum<1>(a, part + blk);
+    if constexpr ((FB & 1) != 0) {
+        __syncthreads();
+        a[0] = acc[1];
+        block_reduce_sum<1>(a, Y.pu + blk);
+    }
+    if constexpr ((FB & 2) != 0) {
+        __syncthreads();
+        a[0] = acc[2];
+        block_reduce_sum<1>(a, Y.pv + blk);
+    }
+}
 
 // the scalar's ghosts: across face k (0 W, 1 E, 2 S, 3 N) q_g = neu[k] ? q : -q + c[k] (c = 2 x the Dirichlet
 // value).  Rectangles: per side; the topology argument is where a masked domain's per-edge table would go
@@ -2071,13 +2121,16 @@ __device__ __forceinline__ void scalar_cell(const Geo& g, const ScalarBC& B, dou
 }
 
 // the thread-per-cell form (NSGPU_CELL=grid): the strips' equivalence oracle; partials sum rT^2 per block
+// (FB != 0: the buoyant variant, as k_rhs_t's)
+template <int FB>
 __global__ __launch_bounds__(256) void k_rhs_t_grid(Geo g, Coef c, ScalarBC B, double dt, double pe,
                                                     const double* __restrict__ u, const double* __restrict__ v,
                                                     const double* __restrict__ q, double* __restrict__ cq,
-                                                    double* __restrict__ rq, double* __restrict__ part, int rows) {
+                                                    double* __restrict__ rq, double* __restrict__ part, int rows,
+                                                    BuoyDev BY) {
     const int j = blockIdx.x * 64 + threadIdx.x;
     const int lend = min((int)(blockIdx.y + 1) * 4 * rows, g.nxl);
-    double acc[1] = {0.0};
+    double acc[FB ? 3 : 1] = {};
     for (int li = blockIdx.y * 4 * rows + threadIdx.y; li < lend && j < g.ny; li += 4) {
         const int ld = g.ld, gi = g.i0 + li;
         const ptrdiff_t o = (ptrdiff_t)li * ld + j;
@@ -2091,8 +2144,9 @@ __global__ __launch_bounds__(256) void k_rhs_t_grid(Geo g, Coef c, ScalarBC B, d
         cq[o] = cn;
         rq[o] = r;
         acc[0] += r * r;
+        if constexpr (FB != 0) buoy_cell<FB>(BY, dt, o, q[o], acc);
     }
-    block_reduce_sum<1>(acc, part + (blockIdx.x + gridDim.x * blockIdx.y));
+    buoy_partials<FB>(BY, acc, part, blockIdx.x + gridDim.x * blockIdx.y);
 }
 
 // k_rhs_t: the scalar's right-hand side as k_rhs_s's strips.  A wave owns 128 columns (2 per lane, 124
@@ -2115,13 +2169,15 @@ struct RhsTArgs {
     int ilo, ihi, jhi;            // written cells: local rows [ilo, ihi), columns [2, jhi)
     int nsblk, nring, nstr;
     RhsRingArgs R;
+    BuoyDev Y;                    // k_rhs_t<.., FB != 0>
 };
+template <int FB>
 __device__ __forceinline__ void rhs_t_ring(const RhsTArgs& A, int blk) {
     const Geo& g = A.g;
     const Coef& c = A.c;
     const RhsRingArgs& R = A.R;
     const int k = blk * 256 + threadIdx.x;
-    double acc[1] = {0.0};
+    double acc[FB ? 3 : 1] = {};
     if (k < R.n) {
         int li, j;
         R.cell(k, g.ny, li, j);
@@ -2137,21 +2193,27 @@ __device__ __forceinline__ void rhs_t_ring(const RhsTArgs& A, int blk) {
         A.cq[o] = cn;
         A.rq[o] = r;
         acc[0] = r * r;
+        if constexpr (FB != 0) buoy_cell<FB>(A.Y, A.dt, o, A.q[o], acc);
     }
-    block_reduce_sum<1>(acc, A.part + A.nstr + blk);
+    buoy_partials<FB>(A.Y, acc, A.part, A.nstr + blk);
 }
 // rows in flight (A/B: make variant DEFS=-DRHS_T_SK=n)
 #ifndef RHS_T_SK
 #define RHS_T_SK 2
 #endif
-template <bool NT, int SK>
+// FB: the buoyant variant (bit 0: x forced, bit 1: y forced; 0: the plain kernel).  Row m of the forced component's
+// RHS and explicit-term planes rides with v and cT0 (the same 16-byte loads and row skew), sc_buoy rewrites both
+// with the row's T (T1) and they go back in place under the same predicate: +32 B/cell per component in the
+// same pass (80 B/cell y only, 112 both), and sum ru'^2 / rv'^2 under acc0's rules
+template <bool NT, int SK, int FB = 0>
 __global__ __launch_bounds__(256) void k_rhs_t(RhsTArgs A) {
     const Geo& g = A.g;
     const Coef& c = A.c;
     if ((int)blockIdx.x >= A.nsblk) {   // the wall ring's workgroups, after the strips' (block-uniform)
-        rhs_t_ring(A, (int)blockIdx.x - A.nsblk);
+        rhs_t_ring<FB>(A, (int)blockIdx.x - A.nsblk);
         return;
     }
+    constexpr int NF = (FB & 1) + (FB >> 1 & 1);   // forced components: slot 0 the first of (x, y), slot 1 y of both
     const int sbx = (int)blockIdx.x;
     // per row: hx, 1/hx, 2/(h_{i-1}+h_i), 2/(h_i+h_{i+1})
     __shared__ double rcs[4][K1_LMAX + 2 * RC_K1 + 2][4];
@@ -2174,6 +2236,12 @@ __global__ __launch_bounds__(256) void k_rhs_t(RhsTArgs A) {
     }
     __syncthreads();
     double acc0 = 0.0;
+    double accf[2] = {0.0, 0.0};
+    // the forced planes per slot: RHS, explicit term, coefficient, partials
+    double* const fr[2] = {(FB & 1) ? A.Y.ru : A.Y.rv, A.Y.rv};
+    double* const fe[2] = {(FB & 1) ? A.Y.cu : A.Y.cv, A.Y.cv};
+    const double fk[2] = {(FB & 1) ? A.Y.bx : A.Y.by, A.Y.by};
+    double* const fp[2] = {(FB & 1) ? A.Y.pu : A.Y.pv, A.Y.pv};
     if (w < nstr) {
         const int ny = g.ny, ld = g.ld;
         const int jb = sj * SW;
@@ -2189,14 +2257,31 @@ __global__ __launch_bounds__(256) void k_rhs_t(RhsTArgs A) {
         const int rlo = -HALO, rhi = g.nxl + HALO - 1;
         const __amdgpu_buffer_rsrc_t bcq = __builtin_amdgcn_make_buffer_rsrc(A.cq, (short)0, 0x7FFFFFF0, 0x00020000);
         const __amdgpu_buffer_rsrc_t brq = __builtin_amdgcn_make_buffer_rsrc(A.rq, (short)0, 0x7FFFFFF0, 0x00020000);
+        __amdgpu_buffer_rsrc_t bfr[2], bfe[2];
+        if constexpr (NF > 0) {
+#pragma unroll
+            for (int k = 0; k < NF; k++) {
+                bfr[k] = __builtin_amdgcn_make_buffer_rsrc(fr[k], (short)0, 0x7FFFFFF0, 0x00020000);
+                bfe[k] = __builtin_amdgcn_make_buffer_rsrc(fe[k], (short)0, 0x7FFFFFF0, 0x00020000);
+            }
+        }
         // one row of u, T (row r) and of v, cT0 (row r-2, the output row of that step): SK rows in flight
+        // (and of the forced components' RHS and explicit term, row r-2)
         double2 QU[SK], QT[SK], QV[SK], QC[SK];
-        auto load = [&](int r, double2& qu, double2& qt, double2& qv, double2& qc) {
+        double2 QR[NF ? NF : 1][SK], QE[NF ? NF : 1][SK];
+        auto load = [&](int r, double2& qu, double2& qt, double2& qv, double2& qc, int q) {
             const int lr = min(max(r, rlo), rhi), lo = min(max(r - 2, 0), g.nxl - 1);
             qu = *reinterpret_cast<const double2*>(A.u + (ptrdiff_t)lr * ld + lc);
             qt = *reinterpret_cast<const double2*>(A.q + (ptrdiff_t)lr * ld + lc);
             qv = *reinterpret_cast<const double2*>(A.v + (ptrdiff_t)lo * ld + lc);
             qc = *reinterpret_cast<const double2*>(A.cq + (ptrdiff_t)lo * ld + lc);
+            if constexpr (NF > 0) {
+#pragma unroll
+                for (int k = 0; k < NF; k++) {
+                    QR[k][q] = *reinterpret_cast<const double2*>(fr[k] + (ptrdiff_t)lo * ld + lc);
+                    QE[k][q] = *reinterpret_cast<const double2*>(fe[k] + (ptrdiff_t)lo * ld + lc);
+                }
+            }
         };
         // windows: u rows r-2 .. r, T rows r-3 .. r; x-slopes of row r-2 (SP*); the x-face (r-3 | r-2)'s flux
         double2 U1 = {0, 0}, U2 = {0, 0}, U3 = {0, 0};
@@ -2205,7 +2290,7 @@ __global__ __launch_bounds__(256) void k_rhs_t(RhsTArgs A) {
         auto xslope = [&](double qm, double qc, double qp, const double* rw) {
             return minmode_nd((qp - qc) * rw[3], (qc - qm) * rw[2]);
         };
-        auto step = [&](const double2 qu, const double2 qt, const double2 qv, const double2 c0v, int r) {
+        auto step = [&](const double2 qu, const double2 qt, const double2 qv, const double2 c0v, int r, int q) {
             U1 = U2; U2 = U3; U3 = vcopy(qu);
             T0 = T1; T1 = T2; T2 = T3; T3 = vcopy(qt);
             const double* rm = rc[r - 2 - ib + RC_K1];   // output row m = r-2
@@ -2251,6 +2336,17 @@ __global__ __launch_bounds__(256) void k_rhs_t(RhsTArgs A) {
             };
             st2(bcq, cn);
             st2(brq, rr);
+            if constexpr (NF > 0) {
+#pragma unroll
+                for (int k = 0; k < NF; k++) {
+                    double fr2[2] = {QR[k][q].x, QR[k][q].y}, fe2[2] = {QE[k][q].x, QE[k][q].y};
+                    sc_buoy(fk[k], T1.x, A.Y.tref, dt, fr2[0], fe2[0]);
+                    sc_buoy(fk[k], T1.y, A.Y.tref, dt, fr2[1], fe2[1]);
+                    if (live && wr && m >= g.sr0 && m < g.sr1) accf[k] += fr2[0] * fr2[0] + fr2[1] * fr2[1];
+                    st2(bfr[k], fr2);
+                    st2(bfe[k], fe2);
+                }
+            }
             FW = FE;
             SPu = SCu; SPt = SCt;
         };
@@ -2258,20 +2354,28 @@ __global__ __launch_bounds__(256) void k_rhs_t(RhsTArgs A) {
         const int r0 = ib - 2, r1 = ie + 1;
 #pragma unroll
         for (int q = 0; q < SK; q++) {
-            load(r0 + q, QU[q], QT[q], QV[q], QC[q]);
+            load(r0 + q, QU[q], QT[q], QV[q], QC[q], q);
             asm volatile("" ::: "memory");
         }
         for (int r = r0; r <= r1; r += SK) {
 #pragma unroll
             for (int q = 0; q < SK; q++) {   // (rows past r1: computed, not stored)
-                step(QU[q], QT[q], QV[q], QC[q], r + q);
-                load(r + q + SK, QU[q], QT[q], QV[q], QC[q]);
+                step(QU[q], QT[q], QV[q], QC[q], r + q, q);
+                load(r + q + SK, QU[q], QT[q], QV[q], QC[q], q);
             }
         }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) acc0 += __shfl_xor(acc0, off, 64);
     if (lane == 0 && w < nstr) A.part[wid] = acc0;
+    if constexpr (NF > 0) {
+#pragma unroll
+        for (int k = 0; k < NF; k++) {
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) accf[k] += __shfl_xor(accf[k], off, 64);
+            if (lane == 0 && w < nstr) fp[k][wid] = accf[k];
+        }
+    }
 }
 
 // (min, -max) of a plane's own cells per block: the scalar's monitor
@@ -5324,14 +5428,33 @@ int launch_rhs(const Knobs& kn, const Geo& g, const Coef& c, double dt, double r
 
 int launch_rhs_t(const Knobs& kn, const Geo& g, const Coef& c, const int* tneu, const double* tc, double dt, double pe,
                  const double* u, const double* v, const double* q, double* cq, double* rq, double* part,
-                 hipStream_t st) {
+                 hipStream_t st, const Buoy* by) {
     if (g.fc || g_phase != 0 || g.nxl != g.nx) return -1;   // (one rank's rectangle: ns_scalar_enable refuses the rest)
     ScalarBC B{};
     for (int k = 0; k < 4; k++) { B.neu[k] = tneu[k]; B.c[k] = tc[k]; }
+    // the forced components (none: exactly the plain kernels); their partials follow each other in by->part, the
+    // returned count apart
+    const int fb = by ? (by->bx != 0.0 ? 1 : 0) | (by->by != 0.0 ? 2 : 0) : 0;
+    BuoyDev Y{};
+    if (fb) {
+        if (!by->ru || !by->rv || !by->cu || !by->cv || !by->part) return -1;
+        Y.bx = by->bx; Y.by = by->by; Y.tref = by->tref;
+        Y.ru = by->ru; Y.rv = by->rv; Y.cu = by->cu; Y.cv = by->cv;
+    }
+    auto partials = [&](int nb) {
+        Y.pu = (fb & 1) ? by->part : nullptr;
+        Y.pv = (fb & 2) ? by->part + ((fb & 1) ? nb : 0) : nullptr;
+    };
     if (kn.cell_grid) {   // NSGPU_CELL=grid: thread per cell
         const int rows = cell_rows(g);
         const dim3 cg = cell_grid(g, rows);
-        NS_LAUNCH(k_rhs_t_grid, cg, dim3(64, 4), 0, st, g, c, B, dt, pe, u, v, q, cq, rq, part, rows);
+        partials((int)(cg.x * cg.y));
+        switch (fb) {
+        case 0: NS_LAUNCH(k_rhs_t_grid<0>, cg, dim3(64, 4), 0, st, g, c, B, dt, pe, u, v, q, cq, rq, part, rows, Y); break;
+        case 1: NS_LAUNCH(k_rhs_t_grid<1>, cg, dim3(64, 4), 0, st, g, c, B, dt, pe, u, v, q, cq, rq, part, rows, Y); break;
+        case 2: NS_LAUNCH(k_rhs_t_grid<2>, cg, dim3(64, 4), 0, st, g, c, B, dt, pe, u, v, q, cq, rq, part, rows, Y); break;
+        default: NS_LAUNCH(k_rhs_t_grid<3>, cg, dim3(64, 4), 0, st, g, c, B, dt, pe, u, v, q, cq, rq, part, rows, Y); break;
+        }
         return (int)(cg.x * cg.y);
     }
     RhsTArgs A{};
@@ -5341,7 +5464,10 @@ int launch_rhs_t(const Knobs& kn, const Geo& g, const Coef& c, const int* tneu, 
     A.ilo = std::max(0, std::min(2 - g.i0, g.nxl));
     A.ihi = std::max(A.ilo, std::min(g.nx - 2 - g.i0, g.nxl));
     A.nsj = (g.ny + SW - 1) / SW;
-    const void* kk = (const void*)k_rhs_t<true, RHS_T_SK>;
+    const void* kk = fb == 0   ? (const void*)k_rhs_t<true, RHS_T_SK>
+                     : fb == 1 ? (const void*)k_rhs_t<true, RHS_T_SK, 1>
+                     : fb == 2 ? (const void*)k_rhs_t<true, RHS_T_SK, 2>
+                               : (const void*)k_rhs_t<true, RHS_T_SK, 3>;
     {
         // the fewest rows that keep every strip in one resident round, as K1's
         const long nsi = std::max(1L, resident_waves(kn, kk) / A.nsj);
@@ -5353,7 +5479,13 @@ int launch_rhs_t(const Knobs& kn, const Geo& g, const Coef& c, const int* tneu, 
     A.R.plan(g.nxl, g.ny, A.ilo, A.ihi, A.jhi);
     A.nring = (A.R.n + 255) / 256;
     A.nsblk = (A.nsj * A.P.nrun + 3) / 4;
-    if (!inner) (void)hipMemsetAsync(part, 0, sizeof(double) * A.nstr, st);   // (no inner cells: zero partials)
+    partials(A.nstr + A.nring);
+    A.Y = Y;
+    if (!inner) {   // (no inner cells: zero partials)
+        (void)hipMemsetAsync(part, 0, sizeof(double) * A.nstr, st);
+        if (Y.pu) (void)hipMemsetAsync(Y.pu, 0, sizeof(double) * A.nstr, st);
+        if (Y.pv) (void)hipMemsetAsync(Y.pv, 0, sizeof(double) * A.nstr, st);
+    }
     void* args[] = {&A};
     if (launch_raw(kk, dim3(A.nsblk + A.nring), dim3(256), args, 0, st) != hipSuccess) return -1;
     return A.nstr + A.nring;

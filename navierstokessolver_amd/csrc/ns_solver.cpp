@@ -374,6 +374,9 @@ struct ns_solver {
         // the min / max of its result, before the velocities' Helmholtz solve, whose residual check brings them
         int next = 4, ok_steps = 0, sweeps = 0, timed = 0;
         ns_scalar_stats last{};
+        // Boussinesq buoyancy (ns_scalar_buoyancy): f = (bx, by) (T - tref), applied by k_rhs_t's buoyant variant
+        double bx = 0.0, by = 0.0, tref = 0.0;
+        bool buoyant() const { return on && (bx != 0.0 || by != 0.0); }
     } sc;
 };
 
@@ -3459,7 +3462,9 @@ int rhs(ns_solver* s, bool defer_norm = false) {
         // (the min / max and ||RHS||^2 partials in one launch; one rank: no bus, no all-reduce)
         // (r7) the host alone reads their results, after the Helmholtz pass: that check's reduction launch takes
         // them along (helm_solve, launch_reduce_step) instead of a launch of their own on the chain behind K1'
-        if (NS_TAILS) s->k1_red_nb = nb;
+        // (buoyancy: scalar_rhs overwrites the forced components' norms right behind this launch -- no deferring,
+        // or the stale norms would land on top of them)
+        if (NS_TAILS && !s->sc.buoyant()) s->k1_red_nb = nb;
         else nsg::launch_reduce_sum_min(ps, nb, 2, s->scal + S_HBN, mm, nb, 4, s->scal + S_MM, s->st);
         return 0;
     } else {
@@ -3569,14 +3574,26 @@ int scalar_rhs(ns_solver* s) {
             if (!e) HIPCHK(hipEventCreate(&e));
         CHK(t_begin(s, q.kev[0], q.kev[1]));
     }
+    // buoyancy: the variant that also folds the force into K1's RU / RV and CU / CV (which then hold convective-minus-
+    // force) and sums the rewritten planes' squares into the partial block's third quarter
+    double* pf = q.part + 4 * (size_t)nsg::max_partials(s->g);
+    const nsg::Buoy by{q.bx, q.by, q.tref, s->arr[NS_ARR_RU], s->arr[NS_ARR_RV], s->arr[NS_ARR_CU], s->arr[NS_ARR_CV], pf};
+    const bool fb = q.buoyant();
     const int nb = nsg::launch_rhs_t(s->k, s->g, s->c, q.neu, q.c, s->dt, q.pe, s->arr[NS_ARR_U], s->arr[NS_ARR_V], q.T,
-                                     q.C, q.R, q.part, s->st);
+                                     q.C, q.R, q.part, s->st, fb ? &by : nullptr);
     if (nb < 0) { set_err("the scalar's right-hand side: launch refused"); return NS_EHIP; }
     if (s->timing && s->in_step) {
         CHK(t_end(s, q.kev[0], q.kev[1]));
         q.timed = 1;
     }
     nsg::launch_reduce_sum(q.part, nb, 1, q.scal + ns_solver::Scalar::BN2, s->st);
+    // the Helmholtz tolerance is relative to ||RHS||^2 (S_HBN): K1's norms of the forced components are stale -- for
+    // a fluid at rest 0, which no residual is below -- so the rewritten planes' own norms replace them here, on the
+    // stream behind K1's reduction (rhs() does not defer it while buoyancy is on) and before the Helmholtz check's read
+    if (fb) {
+        const int nf = (q.bx != 0.0) + (q.by != 0.0);
+        nsg::launch_reduce_sum_segs(pf, nb, nf, s->scal + S_HBN + (q.bx != 0.0 ? 0 : 1), s->st);
+    }
     return 0;
 }
 
@@ -4975,8 +4992,39 @@ int ns_scalar_kernel(ns_solver* s, int which, double* out) {
         if (out) { out[0] = q.last.it_t; out[1] = q.last.res_t; }
         return 0;
     }
+    if (which == 3) {
+        // the right-hand side with the buoyancy force applied to RU / RV / CU / CV as they stand; the forced planes'
+        // norms are the kernel's own (what the step puts into S_HBN), an unforced plane's a plain sum
+        CHK(scalar_rhs(s));
+        const bool fx = q.buoyant() && q.bx != 0.0, fy = q.buoyant() && q.by != 0.0;
+        const int comp[2] = {NS_ARR_RU, NS_ARR_RV};
+        const bool forced[2] = {fx, fy};
+        for (int k = 0; k < 2; k++) {
+            if (forced[k]) continue;
+            const int nb = nsg::launch_sums(s->g, s->arr[comp[k]], q.part, s->st);
+            nsg::launch_reduce_sum(q.part, nb, 2, q.scal + S::AUX, s->st);
+            HIPCHK(hipMemcpyAsync(s->scal + S_HBN + k, q.scal + S::AUX + 1, sizeof(double), hipMemcpyDeviceToDevice, s->st));
+        }
+        HIPCHK(hipMemcpyAsync(q.hs, q.scal, S::NSLOT * sizeof(double), hipMemcpyDeviceToHost, s->st));
+        CHK(fetch(s));
+        if (out) { out[0] = q.hs[S::BN2]; out[1] = s->hs[S_HBN]; out[2] = s->hs[S_HBN + 1]; }
+        return 0;
+    }
     set_err("ns_scalar_kernel: unknown kernel %d", which);
     return NS_EINVAL;
+}
+
+int ns_scalar_buoyancy(ns_solver* s, const ns_buoyancy_desc* d) {
+    CHK(scalar_check(s, "ns_scalar_buoyancy"));
+    if (!d) { set_err("ns_scalar_buoyancy: null descriptor"); return NS_EINVAL; }
+    if (!std::isfinite(d->bx) || !std::isfinite(d->by) || !std::isfinite(d->tref)) {
+        set_err("ns_scalar_buoyancy: bx = %g, by = %g, tref = %g should be finite", d->bx, d->by, d->tref);
+        return NS_EINVAL;
+    }
+    s->sc.bx = d->bx;
+    s->sc.by = d->by;
+    s->sc.tref = d->tref;
+    return 0;
 }
 
 int ns_mg_transfer(ns_solver* s, int op, double* coarse) {

@@ -208,9 +208,17 @@ class GpuSolver:
         L.check(L.lib().ns_scalar_last(self._h, ctypes.byref(st)))
         return st.as_dict()
 
+    def set_buoyancy(self, by: float, bx: float = 0.0, tref: float = 0.0) -> None:
+        """Boussinesq buoyancy: the body force (bx, by) (T - tref) in the momentum equation (ns_scalar_buoyancy).
+        After enable_scalar, between steps; all zero switches it off.  While it is on, NS_ARR_CU / NS_ARR_CV hold
+        the convective term minus the force."""
+        desc = L.NsBuoyancyDesc(float(bx), float(by), float(tref))
+        L.check(L.lib().ns_scalar_buoyancy(self._h, ctypes.byref(desc)))
+
     def scalar_kernel(self, which: int) -> np.ndarray:
-        """ns_scalar_kernel (tests): 1 = the right-hand side alone, 2 = the converged solve of the current rT."""
-        out = np.zeros(2, dtype=np.float64)
+        """ns_scalar_kernel (tests): 1 = the right-hand side alone, 2 = the converged solve of the current rT,
+        3 = the right-hand side with the buoyancy force applied to RU / RV / CU / CV (three values)."""
+        out = np.zeros(3 if which == 3 else 2, dtype=np.float64)
         L.check(L.lib().ns_scalar_kernel(self._h, which, _dptr(out)))
         return out
 
