@@ -1015,9 +1015,9 @@ __device__ inline double piv_next(const FpsArgs& a, int gi, int k, double mu, do
 // a wave whose modes all converge (k >= kfast) reads 1 / p of rows < prow from the table and the converged
 // 1 / p after (pinf); the last global row (no east neighbour) and the slow modes keep piv_next
 // (pb: the first global row of this mode block's fixed point -- 0 with the table, prowb's entry without)
-__device__ inline int fps_prow_block(const FpsArgs& a) {
-    if (a.prowb) return a.prowb[blockIdx.x];
-    return a.ptab && (int)(blockIdx.x * 128) >= a.kfast ? 0 : (1 << 30);
+__device__ inline int fps_prow_block(const FpsArgs& a, int b = blockIdx.x) {
+    if (a.prowb) return a.prowb[b];
+    return a.ptab && (int)(b * 128) >= a.kfast ? 0 : (1 << 30);
 }
 __device__ inline void piv_pair(const FpsArgs& a, bool fast, double2 pinf, int gi, int k0, const double (&mu)[2],
                                 double (&r)[2], double pw, double pe, double pem, double& g0, double& g1, int pb) {
@@ -1092,6 +1092,34 @@ struct ChunkRows {
         }
     }
 };
+
+// (r8) chunk c of this workgroup's mode block is FIXED (FpsArgs::cfix) -- uniform over the wave for a uniform c
+__device__ inline bool fps_chunk_fixed(const FpsArgs& a, int c, int b = blockIdx.x) {
+    if (!NS_FPS_FIXED || !a.cfix) return false;
+    return c <= a.clast && c >= a.cfix[b];
+}
+// every chunk of group grp is FIXED in mode block b (then P, beta and BR of its chunks are the block's one row of
+// FpsArgs::fixv, where that is given)
+__device__ inline bool fps_group_fixed(const FpsArgs& a, int b, int grp) {
+    if (!NS_FPS_FIXED || !a.cfix) return false;
+    return grp * FPS_G + FPS_G - 1 <= a.clast && grp * FPS_G >= a.cfix[b];
+}
+
+// (r8) with FIXED chunks the workgroups of mode block 0 -- the lowest modes, last or never at their fixed point: a
+// division per row in the general body -- are the pass's long ones: a workgroup's (block, group) taken from its place in
+// dispatch order so that block 0's come first and run beside the streaming ones instead of after them (4096^2:
+// k_fps_t1b 37.7 -> 30.4 us, k_fps_t2b 48.3 -> 45.0 us).  A permutation of the grid: no value changes
+__device__ inline void fps_block0_first(const FpsArgs& a, int& bx, int& by) {
+    if (!NS_FPS_FIXED || !a.cfix || gridDim.x < 2) return;
+    const int nbx = gridDim.x, ng = gridDim.y, L = by * nbx + bx;
+    if (L < ng) {
+        bx = 0;
+        by = L;
+    } else {
+        bx = 1 + (L - ng) % (nbx - 1);
+        by = (L - ng) / (nbx - 1);
+    }
+}
 
 // T1: per chunk the forward recurrence from zero -> (E, Pi) into ca; the workgroup folds its chunks
 // into the group's aggregate ga (y_out = E + Pi y_in)
@@ -1470,11 +1498,46 @@ __global__ void __launch_bounds__(64 * FPS_G) k_fps_t3(FpsArgs a, double* __rest
 __global__ void __launch_bounds__(64 * FPS_G) k_fps_t1b(FpsArgs a, const double* __restrict__ f) {
     __shared__ double2 sE[FPS_G][64], sP[FPS_G][64];
     const int lane = threadIdx.x, w = __builtin_amdgcn_readfirstlane(threadIdx.y);
-    const int k0 = 2 * (blockIdx.x * 64 + lane);
-    const int grp = FPS_SNAKE ? (int)gridDim.y - 1 - (int)blockIdx.y : (int)blockIdx.y, c = grp * FPS_G + w;
+    int bx = blockIdx.x, by = blockIdx.y;
+    fps_block0_first(a, bx, by);
+    const int k0 = 2 * (bx * 64 + lane);
+    const int grp = FPS_SNAKE ? (int)gridDim.y - 1 - by : by, c = grp * FPS_G + w;
     const int li0 = c * FPS_M;
     const int rows = k0 < a.ny ? min(FPS_M, a.nxl - li0) : 0;
     double E[2] = {0.0, 0.0}, P[2] = {1.0, 1.0};
+    if (fps_chunk_fixed(a, c, bx)) {   // (uniform over the wave)
+        // (r8) a FIXED chunk (FpsArgs::cfix): every row's pivot is pinf and (pw, pe) one pair, so g = pw r and
+        // q = -pe r are formed once, by the operations the general body below applies per row to the same operands
+        // -- the same bits -- without the chunk's pivots rv[] (64 VGPRs), piv_pair's conditions or the rows' coefficients
+        if (rows > 0) {
+            const double s0 = mode0_shift(a, k0, f);
+            double2 yv[FPS_M];
+#pragma unroll
+            for (int t = 0; t < FPS_M; t++) yv[t] = ldf0(a, f, li0 + t, k0, s0);
+            const double2 pinf = ld2(a.pinf + k0);
+            const double pw = a.pw[a.i0 + li0], pe = a.pe[a.i0 + li0];
+            const double g0 = pw * pinf.x, g1 = pw * pinf.y;
+            const double q0 = -pe * pinf.x, q1 = -pe * pinf.y;
+#pragma unroll
+            for (int t = 0; t < FPS_M; t++) {
+                E[0] = fma(-g0, E[0], yv[t].x);
+                E[1] = fma(-g1, E[1], yv[t].y);
+                P[0] = -g0 * P[0];
+                P[1] = -g1 * P[1];
+                yv[t] = double2{E[0], E[1]};
+            }
+            double xl[2] = {0.0, 0.0};
+#pragma unroll
+            for (int t = FPS_M - 1; t >= 0; t--) {
+                xl[0] = fma(yv[t].x, pinf.x, q0 * xl[0]);
+                xl[1] = fma(yv[t].y, pinf.y, q1 * xl[1]);
+            }
+            st2(a.ca + (size_t)c * a.ld + k0, E[0], E[1]);
+            // (a group of FIXED chunks: k_fps_midscan takes P from fixv, the operator's, not from ca)
+            if (!(a.fixv && fps_group_fixed(a, bx, grp))) st2(a.ca + (size_t)(a.nch + c) * a.ld + k0, P[0], P[1]);
+            st2(a.cb + (size_t)c * a.ld + k0, xl[0], xl[1]);
+        }
+    } else {
     ChunkRows cr;
     cr.load_wave(a, li0);   // (every lane, before the divergent branch)
     if (rows > 0) {
@@ -1486,7 +1549,7 @@ __global__ void __launch_bounds__(64 * FPS_G) k_fps_t1b(FpsArgs a, const double*
         for (int t = 0; t < FPS_M; t++)
             yv[t] = ldf0(a, f, min(li0 + t, a.nxl - 1), k0, s0);   // (r6: unconditional, clamped: pipelined)
         double r[2] = {r0.x, r0.y};
-        const int pb = fps_prow_block(a);
+        const int pb = fps_prow_block(a, bx);
         const bool fast = pb < a.nx;
         const double2 pinf = fast ? ld2(a.pinf + k0) : double2{0.0, 0.0};
 #pragma unroll
@@ -1514,6 +1577,7 @@ __global__ void __launch_bounds__(64 * FPS_G) k_fps_t1b(FpsArgs a, const double*
         st2(a.ca + (size_t)c * a.ld + k0, E[0], E[1]);
         st2(a.ca + (size_t)(a.nch + c) * a.ld + k0, P[0], P[1]);
         st2(a.cb + (size_t)c * a.ld + k0, xl[0], xl[1]);
+    }
     }
     sE[w][lane] = double2{E[0], E[1]};
     sP[w][lane] = double2{P[0], P[1]};
@@ -1545,14 +1609,29 @@ __global__ void __launch_bounds__(64) k_fps_mid(FpsArgs a, const double* __restr
     // (r6) every chunk's loads first (clamped chunk index): inside the uniform `c < nch` branch below they were
     // issued chunk by chunk behind the carry's dependent chain
     double2 le[FPS_G], lp[FPS_G], lb[FPS_G], lbe[FPS_G], lbr[FPS_G];
+    const bool gf = a.fixv && fps_group_fixed(a, blockIdx.x, grp);   // (r8: as k_fps_midscan)
 #pragma unroll
     for (int w = 0; w < FPS_G; w++) {
         const int c = min(grp * FPS_G + w, a.nch - 1);
         le[w] = ld2(a.ca + (size_t)c * a.ld + k0);
-        lp[w] = ld2(a.ca + (size_t)(a.nch + c) * a.ld + k0);
         lb[w] = ld2(a.cb + (size_t)c * a.ld + k0);
-        lbe[w] = ld2(a.bt + (size_t)c * a.ld + k0);
-        lbr[w] = ld2(a.bt + (size_t)(a.nch + c) * a.ld + k0);
+    }
+    if (gf) {
+        const double2 fp = ld2(a.fixv + k0), fbe = ld2(a.fixv + (size_t)a.ld + k0), fbr = ld2(a.fixv + 2 * (size_t)a.ld + k0);
+#pragma unroll
+        for (int w = 0; w < FPS_G; w++) {
+            lp[w] = fp;
+            lbe[w] = fbe;
+            lbr[w] = fbr;
+        }
+    } else {
+#pragma unroll
+        for (int w = 0; w < FPS_G; w++) {
+            const int c = min(grp * FPS_G + w, a.nch - 1);
+            lp[w] = ld2(a.ca + (size_t)(a.nch + c) * a.ld + k0);
+            lbe[w] = ld2(a.bt + (size_t)c * a.ld + k0);
+            lbr[w] = ld2(a.bt + (size_t)(a.nch + c) * a.ld + k0);
+        }
     }
 #pragma unroll
     for (int w = 0; w < FPS_G; w++) {
@@ -1710,14 +1789,31 @@ __global__ void __launch_bounds__(MS_NT) k_fps_midscan(FpsArgs a, const double* 
         double Y[2] = {gc[grp * MS_MB + 2 * pr], gc[grp * MS_MB + 2 * pr + 1]};
         double BX[FPS_G][2], BR[FPS_G][2];
         double2 le[FPS_G], lp[FPS_G], lb[FPS_G], lbe[FPS_G], lbr[FPS_G];
+        // (r8) a group of FIXED chunks: P, beta and BR are one row per mode block (fixv, checked bit for bit against
+        // every chunk's at ns_create), not a row per chunk; a group that mixes FIXED and other chunks loads as before
+        const bool gf = a.fixv && fps_group_fixed(a, k0 / 128, grp);
 #pragma unroll
         for (int w = 0; w < FPS_G; w++) {
             const int c = min(grp * FPS_G + w, a.nch - 1);
             le[w] = ld2(a.ca + (size_t)c * a.ld + k0);
-            lp[w] = ld2(a.ca + (size_t)(a.nch + c) * a.ld + k0);
             lb[w] = ld2(a.cb + (size_t)c * a.ld + k0);
-            lbe[w] = ld2(a.bt + (size_t)c * a.ld + k0);
-            lbr[w] = ld2(a.bt + (size_t)(a.nch + c) * a.ld + k0);
+        }
+        if (gf) {
+            const double2 fp = ld2(a.fixv + k0), fbe = ld2(a.fixv + (size_t)a.ld + k0), fbr = ld2(a.fixv + 2 * (size_t)a.ld + k0);
+#pragma unroll
+            for (int w = 0; w < FPS_G; w++) {
+                lp[w] = fp;
+                lbe[w] = fbe;
+                lbr[w] = fbr;
+            }
+        } else {
+#pragma unroll
+            for (int w = 0; w < FPS_G; w++) {
+                const int c = min(grp * FPS_G + w, a.nch - 1);
+                lp[w] = ld2(a.ca + (size_t)(a.nch + c) * a.ld + k0);
+                lbe[w] = ld2(a.bt + (size_t)c * a.ld + k0);
+                lbr[w] = ld2(a.bt + (size_t)(a.nch + c) * a.ld + k0);
+            }
         }
 #pragma unroll
         for (int w = 0; w < FPS_G; w++) {
@@ -1772,10 +1868,50 @@ __global__ void __launch_bounds__(MS_NT) k_fps_midscan(FpsArgs a, const double* 
 template <bool GHOST>
 __global__ void __launch_bounds__(64 * FPS_G) k_fps_t2b(FpsArgs a, double* __restrict__ f) {
     const int lane = threadIdx.x, w = __builtin_amdgcn_readfirstlane(threadIdx.y);
-    const int k0 = 2 * (blockIdx.x * 64 + lane);
-    const int grp = blockIdx.y, c = grp * FPS_G + w;
+    int bx = blockIdx.x, by = blockIdx.y;
+    if (!GHOST) fps_block0_first(a, bx, by);
+    const int k0 = 2 * (bx * 64 + lane);
+    const int grp = by, c = grp * FPS_G + w;
     const int li0 = c * FPS_M;
     const int rows = k0 < a.ny ? min(FPS_M, a.nxl - li0) : 0;
+    if (!GHOST && fps_chunk_fixed(a, c, bx)) {   // (uniform over the wave)
+        // (r8) a FIXED chunk, as in k_fps_t1b: one (g, q) per mode, no rv[], no piv_pair, no coefficient rows
+        if (rows <= 0) return;
+        const double s0 = mode0_shift(a, k0);
+        double2 yv[FPS_M];
+#pragma unroll
+        for (int t = 0; t < FPS_M; t++) yv[t] = ldf0(a, f, li0 + t, k0, s0);
+        const double2 yin = ld2(a.ya + (size_t)c * a.ld + k0);
+        const double2 x0 = ld2(a.gx + (size_t)grp * a.ld + k0);
+        double X[2] = {x0.x, x0.y};
+        for (int q = FPS_G - 1; q > w; q--) {
+            const int cq = grp * FPS_G + q;
+            if (cq >= a.nch) continue;
+            // (cq > c: FIXED up to clast, where BR is the block's one row of fixv)
+            const double* brp = a.fixv && cq <= a.clast ? a.fixv + 2 * (size_t)a.ld : a.bt + (size_t)(a.nch + cq) * a.ld;
+            const double2 bx = ld2(a.cb + (size_t)cq * a.ld + k0), br = ld2(brp + k0);
+            X[0] = fma(br.x, X[0], bx.x);
+            X[1] = fma(br.y, X[1], bx.y);
+        }
+        const double2 pinf = ld2(a.pinf + k0);
+        const double pw = a.pw[a.i0 + li0], pe = a.pe[a.i0 + li0];
+        const double g0 = pw * pinf.x, g1 = pw * pinf.y;
+        const double q0 = -pe * pinf.x, q1 = -pe * pinf.y;
+        double y[2] = {yin.x, yin.y};
+#pragma unroll
+        for (int t = 0; t < FPS_M; t++) {
+            y[0] = fma(-g0, y[0], yv[t].x);
+            y[1] = fma(-g1, y[1], yv[t].y);
+            yv[t] = double2{y[0], y[1]};
+        }
+#pragma unroll
+        for (int t = FPS_M - 1; t >= 0; t--) {
+            X[0] = fma(yv[t].x, pinf.x, q0 * X[0]);
+            X[1] = fma(yv[t].y, pinf.y, q1 * X[1]);
+            st2(f + (size_t)(li0 + t) * a.ld + k0, X[0], X[1]);
+        }
+        return;
+    }
     ChunkRows cr;
     cr.load_wave(a, li0);   // (every lane, before the divergent return)
     if (rows <= 0) return;
@@ -1800,7 +1936,7 @@ __global__ void __launch_bounds__(64 * FPS_G) k_fps_t2b(FpsArgs a, double* __res
     const double2 r0 = ld2(a.rp0 + (size_t)c * a.ld + k0);
     double r[2] = {r0.x, r0.y}, y[2] = {yin.x, yin.y};
     double2 rv[FPS_M];
-    const int pb = fps_prow_block(a);
+    const int pb = fps_prow_block(a, bx);
     const bool fast = pb < a.nx;
     const double2 pinf = fast ? ld2(a.pinf + k0) : double2{0.0, 0.0};
 #pragma unroll

@@ -11,6 +11,10 @@
 #define NS_TAILS 1   // (r7) 0: K1''s reduction and the direct solve's group scans keep their own launches (A/B: make
                      // variant V=notails DEFS="-DNS_TAILS=0")
 #endif
+#ifndef NS_FPS_FIXED
+#define NS_FPS_FIXED 1   // (r8) 0: k_fps_t1b / k_fps_t2b run the general body on every chunk (A/B: make variant V=nofixed
+                         // DEFS="-DNS_FPS_FIXED=0")
+#endif
 
 namespace nsg {
 
@@ -402,6 +406,16 @@ struct FpsArgs {
     // sit at their fixed point (prowb, ld / 128 ints; 1 << 30: never) -- rows before it keep the division, rows
     // after it take pinf.  The table's reads (up to 1024 rows x ld) cost t1b more than the divisions they saved
     const int* prowb = nullptr;
+    // (r8, one rank, x uniform, prowb's blocks) per 128-mode block the first chunk from which every chunk up to clast
+    // is FIXED: its entry pivot is pinf, its rows and the row before them share one (pw, pe), it is whole and does not
+    // hold global row nx - 1 (cfix, next to prowb; 1 << 30: never) -- t1b / t2b run their constant-coefficient body
+    // there.  null: none
+    const int* cfix = nullptr;
+    int clast = -1;
+    // (r8) the FIXED chunks' operator tables collapsed: P (ca's second half), beta and BR (bt's halves) are the same
+    // row for every FIXED chunk of a block -- 3 x ld, checked bit for bit at ns_create (P against a run of k_fps_t1b
+    // itself; a block that fails has no FIXED chunks).  Groups of FIXED chunks read these, and t1b stores no P there
+    const double* fixv = nullptr;
     // (r5, one allgather per solve) k_fps_mid's first, rank-local pass: only the groups' backward aggregates (the
     // chunks' carries and BX are formed again after the allgather)
     int mid_local = 0;

@@ -2740,8 +2740,45 @@ int fps_setup(ns_solver* s, const std::vector<double>& hy, const double* pw, con
             }
         }
     }
-    // (the pivot table and pinf, or pinf and the block rows -- ints, in doubles' room)
-    const size_t n_pt = !ptab.empty() ? ptab.size() + (size_t)ld : (!prowb.empty() ? (size_t)ld + prowb.size() : 0);
+    // (r8) the FIXED chunks of t1b / t2b (FpsArgs::cfix), each condition compared bit for bit on the tables the
+    // device reads: from cfix[b] to clast every chunk of block b starts at the fixed point (rp0 = pinf, and past
+    // prowb so that the general body takes pinf there too), is whole, does not hold global row nx - 1, and its rows
+    // and the row before them share one (pw, pe).  One rank without an outflow side only
+    std::vector<int> cfix;
+    int clast = -1;
+    int* d_cfix = nullptr;
+    double* d_fixv = nullptr;
+    if (NS_FPS_FIXED && !prowb.empty() && s->nranks == 1 && g.i0 == 0 && g.nxl == g.nx && !a.outE) {
+        const int nb = (int)prowb.size();
+        auto plain = [&](int c) {   // (the conditions that do not depend on the block)
+            const int gi0 = c * nsg::FPS_M;
+            if (gi0 < 1 || gi0 + nsg::FPS_M > g.nx - 1) return false;
+            for (int gi = gi0; gi < gi0 + nsg::FPS_M; gi++)
+                if (std::memcmp(&pw[gi], &pw[gi0 - 1], sizeof(double)) || std::memcmp(&pe[gi], &pe[gi0 - 1], sizeof(double)))
+                    return false;
+            return true;
+        };
+        for (int c = a.nch - 1; c >= 0 && clast < 0; c--)
+            if (plain(c)) clast = c;
+        cfix.assign(nb, 1 << 30);
+        long nfix = 0;
+        for (int b = 0; b < nb && clast >= 0; b++) {
+            if (prowb[b] >= g.nx) continue;
+            const int k1 = std::min(N, (b + 1) * 128);
+            for (int c = clast; c >= 0; c--) {
+                bool ok = plain(c) && c * nsg::FPS_M >= prowb[b];
+                for (int k = b * 128; k < k1 && ok; k++)
+                    ok = std::memcmp(&rp0[(size_t)c * ld + k], &pinf[k], sizeof(double)) == 0;
+                if (!ok) break;
+                cfix[b] = c;
+            }
+            if (cfix[b] <= clast) nfix += clast - cfix[b] + 1;
+        }
+        if (nfix == 0) cfix.clear();
+    }
+    // (the pivot table and pinf, or pinf and the block rows and first fixed chunks -- ints, in doubles' room)
+    // (r8: and the FIXED chunks' collapsed tables, 3 x ld)
+    const size_t n_pt = !ptab.empty() ? ptab.size() + (size_t)ld : (!prowb.empty() ? (size_t)ld + prowb.size() + 3 * (size_t)ld : 0);
     // (r5) ny = 16384: e^{-2 pi i m / 8192}, m < 8192, after the pivot table (the two-half transforms)
     const size_t n_t8 = nsg::fps_log2(N) < 0 ? (size_t)N : 0;
     HIPCHK(hipMalloc(&s->fps_mem, (total + n_pt + n_t8) * sizeof(double)));
@@ -2767,10 +2804,12 @@ int fps_setup(ns_solver* s, const std::vector<double>& hy, const double* pw, con
     } else if (n_pt) {
         double* pt = s->fps_mem + total;
         HIPCHK(hipMemcpy(pt, pinf.data(), (size_t)ld * sizeof(double), hipMemcpyHostToDevice));
-        int* pb = reinterpret_cast<int*>(pt + ld);
+        int* pb = reinterpret_cast<int*>(pt + 4 * (size_t)ld);   // (after pinf and fixv: those are read in pairs)
         HIPCHK(hipMemcpy(pb, prowb.data(), prowb.size() * sizeof(int), hipMemcpyHostToDevice));
         a.pinf = pt;
         a.prowb = pb;
+        d_cfix = pb + prowb.size();
+        d_fixv = pt + ld;
     }
     double* d = s->fps_mem;
     s->fps_tw = d;
@@ -2881,6 +2920,54 @@ int fps_setup(ns_solver* s, const std::vector<double>& hy, const double* pw, con
     }
     a.pw = s->c.pw;
     a.pe = s->c.pe;
+    // (r8) the FIXED chunks' tables collapsed to one row per block (FpsArgs::fixv): P from a run of k_fps_t1b itself
+    // (its general body on every chunk, a zero plane -- P is the operator's), beta and BR from bt; every FIXED chunk's
+    // row must equal its block's first bit for bit, or the block has no FIXED chunks
+    long nfix = 0;
+    if (!cfix.empty() && d_cfix) {
+        const size_t npl = (size_t)g.nxl * ld, nP = (size_t)a.nch * ld;
+        double* zero = nullptr;
+        HIPCHK(hipMalloc(&zero, npl * sizeof(double)));
+        HIPCHK(hipMemsetAsync(zero, 0, npl * sizeof(double), s->st));
+        nsg::launch_fps_t1b(a, zero, s->st);
+        std::vector<double> hP(nP);
+        HIPCHK(hipMemcpyAsync(hP.data(), a.ca + nP, nP * sizeof(double), hipMemcpyDeviceToHost, s->st));
+        HIPCHK(hipStreamSynchronize(s->st));
+        HIPCHK(hipFree(zero));
+        std::vector<double> fv(3 * (size_t)ld, 0.0);
+        const double* tab[3] = {hP.data(), bt, bt + nP};
+        for (int b = 0; b < (int)cfix.size(); b++) {
+            if (cfix[b] > clast) continue;
+            const int k0 = b * 128, nk = std::min(N, k0 + 128) - k0;
+            bool ok = true;
+            for (int q = 0; q < 3 && ok; q++) {
+                const double* row0 = tab[q] + (size_t)cfix[b] * ld + k0;
+                std::memcpy(&fv[(size_t)q * ld + k0], row0, nk * sizeof(double));
+                for (int c = cfix[b] + 1; c <= clast && ok; c++)
+                    ok = std::memcmp(tab[q] + (size_t)c * ld + k0, row0, nk * sizeof(double)) == 0;
+            }
+            if (ok) nfix += clast - cfix[b] + 1;
+            else cfix[b] = 1 << 30;
+        }
+        if (nfix > 0) {
+            HIPCHK(hipMemcpy(d_fixv, fv.data(), fv.size() * sizeof(double), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(d_cfix, cfix.data(), cfix.size() * sizeof(int), hipMemcpyHostToDevice));
+            a.cfix = d_cfix;
+            a.clast = clast;
+            a.fixv = d_fixv;
+        }
+    }
+    if (s->k.verbose && s->rank == 0) {
+        const int nbm = (N + 127) / 128;
+        fprintf(stderr, "nsgpu fps: fixed chunks %ld of %ld (block, chunk) pairs", nfix, (long)nbm * a.nch);
+        if (nfix > 0) {
+            fprintf(stderr, " (%d x %d, last fixed chunk %d); fixed-point rows:", nbm, a.nch, clast);
+            for (int b = 0; b < nbm; b++) fprintf(stderr, prowb[b] >= g.nx ? " -" : " %d", prowb[b]);
+            fprintf(stderr, "; first fixed chunks:");
+            for (int b = 0; b < nbm; b++) fprintf(stderr, cfix[b] > clast ? " -" : " %d", cfix[b]);
+        }
+        fprintf(stderr, "\n");
+    }
     return 0;
 }
 
