@@ -61,7 +61,9 @@ typedef struct ns_solver ns_solver;  /* opaque: device memory, stream, RCCL comm
 
 /* boundary-condition types: bcTypes, Grid.h:6 */
 #define NS_BC_INLET_UNI       0
-#define NS_BC_INLET_PARABOLIC 1  /* rejected: empty ghost constant in the reference (FluidSolver.cpp:86-87,171) */
+#define NS_BC_INLET_PARABOLIC 1  /* rejected by ns_create: empty ghost constant in the reference (FluidSolver.cpp:86-87,
+                                    171).  A developed inflow is an INLET_UNI edge carrying ns_parabolic_profile's
+                                    values as its ns_edge_profile */
 #define NS_BC_WALL            2
 #define NS_BC_PRESSURE        3  /* rejected: no ghost stencil in the reference (FluidSolver.cpp:150,168) */
 #define NS_BC_NEUMANN         4  /* outflow: velocity ghost q, phi ghost 2.5 phi_0 - 2 phi_1 + 0.5 phi_2
@@ -315,7 +317,25 @@ int  ns_scalar_get_rhs(ns_solver* s, double* rT);
 typedef struct ns_buoyancy_desc { double bx, by, tref; } ns_buoyancy_desc;   /* f = (bx, by) (T - tref) */
 int  ns_scalar_buoyancy(ns_solver* s, const ns_buoyancy_desc* d);
 
+/* ---- boundary values that vary along an edge: inlet profiles, shaped lids ----
+ * per-face bcInfo of one WALL / INLET_UNI edge: info[k], k = j (x-normal edge, n == ny) or global i (y-normal
+ * edge, n == nx of the whole grid, on every rank); entries where the edge has no face are ignored.  The ghost
+ * constant of face k is 2 info[k] in the component the edge's own info goes to (an inlet's normal velocity, a
+ * wall's tangential one); K1, the implicit half's wall terms, K3 (fused into the direct solve or not) and the
+ * scalar's right-hand side read it ("Edge profiles").
+ * info == NULL: back to the edge's own value (its ns_edge.info).
+ * Between steps, any number of times (time-dependent inflow); ordered on the solver's stream like ns_scalar_set.
+ * NS_EINVAL (the message names the edge) for a bad edge index, a NEUMANN edge, n different from the box's extent
+ * along the edge, or a value that is not finite.  Flux compatibility of the inlets stays the caller's business.
+ * Additive to ABI 9. */
+int  ns_edge_profile(ns_solver* s, int32_t edge, const double* info, int32_t n);
+
 /* ---- host-side helpers (no GPU needed) ---- */
+/* the face averages of the parabola 6 s (1 - s) * mean over the faces k0 <= k < k1 of spacings h[0..n) (s runs 0..1
+ * from face k0's lower end to face k1-1's upper end), 0 elsewhere: the average over [sa, sb] is
+ * mean (3 (sa + sb) - 2 (sa^2 + sa sb + sb^2)), and sum out[k] h[k] = mean * (the faces' length) up to round-off
+ * on any spacing -- a parabolic and a uniform inlet of the same info carry the same discrete flux */
+int  ns_parabolic_profile(const double* h, int32_t n, int32_t k0, int32_t k1, double mean, double* out);
 /* the x-slab [i0, i1) of `rank` out of `nranks` for nx cells */
 int  ns_slab_range(int32_t nx, int32_t nranks, int32_t rank, int32_t* i0, int32_t* i1);
 /* size in bytes of an ncclUniqueId, and produce one (rank 0 only; needs RCCL, no GPU) */

@@ -130,6 +130,8 @@ SIGNATURES = {
     "ns_scalar_kernel": (ctypes.c_int, [_P, ctypes.c_int, _D]),
     "ns_scalar_get_rhs": (ctypes.c_int, [_P, _D]),
     "ns_scalar_buoyancy": (ctypes.c_int, [_P, ctypes.POINTER(NsBuoyancyDesc)]),
+    "ns_edge_profile": (ctypes.c_int, [_P, ctypes.c_int32, _D, ctypes.c_int32]),
+    "ns_parabolic_profile": (ctypes.c_int, [_D, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, _D]),
     "ns_slab_range": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                      ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "ns_nccl_id_size": (ctypes.c_int, []),

@@ -3,6 +3,8 @@ reference's two input files (grid file Grid.cpp:234-290, sim file
 FluidSolver.cpp:626-669) for a rectangle."""
 from __future__ import annotations
 
+import ctypes
+
 import numpy as np
 
 from . import _lib as L
@@ -75,6 +77,19 @@ def polygon(vertices, hx, hy, bc) -> GridSpec:
 
 def cavity(n, lid=1.0) -> GridSpec:
     return rectangle(n, n, bc=[(L.NS_BC_WALL, 0.0), (L.NS_BC_WALL, lid), (L.NS_BC_WALL, 0.0), (L.NS_BC_WALL, 0.0)])
+
+
+def parabolic_profile(h, k0, k1, mean):
+    """The face averages of the parabola 6 s (1 - s) * mean over the faces k0 <= k < k1 of spacings h (s runs 0..1
+    over them), 0 elsewhere (ns_parabolic_profile): sum(out * h) = mean * sum(h[k0:k1]) up to round-off, so the
+    profile carries a uniform inlet's flux.  GpuSolver.set_edge_profile takes it (a developed inflow: an INLET_UNI
+    edge with this profile)."""
+    h = np.ascontiguousarray(np.asarray(h, dtype=np.float64).ravel())
+    out = np.empty_like(h)
+    dp = ctypes.POINTER(ctypes.c_double)
+    L.check(L.lib().ns_parabolic_profile(h.ctypes.data_as(dp), h.size, int(k0), int(k1), float(mean),
+                                         out.ctypes.data_as(dp)))
+    return out
 
 
 def cavity_dt(n):

@@ -358,8 +358,13 @@ __global__ void __launch_bounds__(Fft<LOGN>::T) FPS_WAVES k_fps_dct(const double
 // step (K3's b written and read back).  Pairs p = plo + q pstep, q < cnt (slabs: the interior pairs,
 // then the two edge pairs after the u*, v* ghost-row exchange); consecutive pairs on one XCD (their
 // shared u* rows in its L2).  The sums go out per row pair (deterministic under any split).
-__device__ inline double fv_ghost(const Geo& g, double q, int side, int d) {
-    return g.neu[side] ? q : (-q + (d == 0 ? g.c0[side] : g.c1[side]));
+// (k: the face's column on W / E, global row on S / N -- an edge profile's index, edge_const; PROF false: the side's own
+// constant and no table test, the code of a solver without profiles)
+template <bool PROF>
+__device__ inline double fv_ghost(const Geo& g, double q, int side, int d, int k) {
+    const double cc = PROF ? edge_const(g.c0[side], g.c1[side], g.pt[side], g.pd[side], d, k, side < 2 ? g.ny : g.nx)
+                           : (d == 0 ? g.c0[side] : g.c1[side]);
+    return g.neu[side] ? q : (-q + cc);
 }
 __device__ inline double dpp_up1(double x) {   // lane l <- lane l - 1
     const int lo = __double2loint(x), hi = __double2hiint(x);
@@ -388,7 +393,7 @@ struct FpsDivArgs {
     int outE;              // (r5) NEUMANN outflow E side: the last row pair's second row transforms b_{n-1} - b_{n-2} / 2
 };
 
-template <int LOGN>
+template <int LOGN, bool PROF = false>
 __global__ void __launch_bounds__(Fft<LOGN>::T) FPS_WAVES k_fps_dct_div(FpsDivArgs A) {
     constexpr int N = Fft<LOGN>::N, T = Fft<LOGN>::T, NC = N / 2;   // column pairs per row
     extern __shared__ cplx z[];
@@ -459,8 +464,8 @@ __global__ void __launch_bounds__(Fft<LOGN>::T) FPS_WAVES k_fps_dct_div(FpsDivAr
                     const double vc = e ? vv.y : vv.x;
                     const double vs = e ? vv.x : (rr ? vsB : vsA), vn = e ? (rr ? vnB : vnA) : vv.y;
                     const bool hW = rr ? hWb : hWa, hE = rr ? hEb : hEa;
-                    const double X = hE ? uev : fv_ghost(g, uc, 1, 0), Y = hW ? uwv : fv_ghost(g, uc, 0, 0);
-                    const double Xn = n ? vn : fv_ghost(g, vc, 3, 1), Ys = s ? vs : fv_ghost(g, vc, 2, 1);
+                    const double X = hE ? uev : fv_ghost<PROF>(g, uc, 1, 0, jj), Y = hW ? uwv : fv_ghost<PROF>(g, uc, 0, 0, jj);
+                    const double Xn = n ? vn : fv_ghost<PROF>(g, vc, 3, 1, gi + rr), Ys = s ? vs : fv_ghost<PROF>(g, vc, 2, 1, gi + rr);
                     d[rr][e] = fma(X - Y, rr ? rhxb : rhxa, (Xn - Ys) * rhy) * hrdt;
                 }
             }
@@ -641,7 +646,7 @@ __device__ inline void rfft_stage(cplx* z, const cplx* __restrict__ tw, int tid,
     __syncthreads();
 }
 
-template <int LOGN>
+template <int LOGN, bool PROF = false>
 __global__ void __launch_bounds__(RFft<LOGN>::T) k_fps_dct_div_r(FpsDivArgs A) {
     constexpr int N = 1 << LOGN, M = N / 2, T = RFft<LOGN>::T, LOGM = LOGN - 1;
     constexpr int NCT = M / T, B = NCT < FPS_RB ? NCT : FPS_RB;   // column pairs per thread (8), loads batched by 4
@@ -693,8 +698,8 @@ __global__ void __launch_bounds__(RFft<LOGN>::T) k_fps_dct_div_r(FpsDivArgs A) {
                              uev = e ? U[q][2].y : U[q][2].x;
                 const double vc = e ? V[q].y : V[q].x;
                 const double vsv = e ? V[q].x : vs, vnv = e ? vn : V[q].y;
-                const double X = hE ? uev : fv_ghost(g, uc, 1, 0), Y = hW ? uwv : fv_ghost(g, uc, 0, 0);
-                const double Xn = na ? vnv : fv_ghost(g, vc, 3, 1), Ys = sa ? vsv : fv_ghost(g, vc, 2, 1);
+                const double X = hE ? uev : fv_ghost<PROF>(g, uc, 1, 0, jj), Y = hW ? uwv : fv_ghost<PROF>(g, uc, 0, 0, jj);
+                const double Xn = na ? vnv : fv_ghost<PROF>(g, vc, 3, 1, gi), Ys = sa ? vsv : fv_ghost<PROF>(g, vc, 2, 1, gi);
                 d[e] = fma(X - Y, rhx, (Xn - Ys) * rhy) * hrdt;
             }
             acc0 += d[0] + d[1];
@@ -2021,30 +2026,30 @@ void dct_pair(const Knobs& k, bool inverse, const double* in, const double* shif
 bool fps_div_real(const Knobs& k, int logn, int outE) {
     return k.fps_real && !outE && logn >= 10 && logn <= 14;
 }
-template <int LOGN>
+template <int LOGN, bool PROF = false>
 int div_row(const FpsDivArgs& a0, hipStream_t st) {
     if constexpr (LOGN >= 10 && LOGN <= 14) {
         constexpr int T = RFft<LOGN>::T;
         const size_t lds = sizeof(cplx) * (size_t)RFft<LOGN>::M;
-        lds_attr_once((const void*)k_fps_dct_div_r<LOGN>, (int)lds);
+        lds_attr_once((const void*)k_fps_dct_div_r<LOGN, PROF>, (int)lds);
         const dim3 grid(2 * a0.cnt);
         hipEvent_t a, b;
-        if (take_launch_timing(a, b)) hipExtLaunchKernelGGL(k_fps_dct_div_r<LOGN>, grid, dim3(T), lds, st, a, b, 0, a0);
-        else hipLaunchKernelGGL(k_fps_dct_div_r<LOGN>, grid, dim3(T), lds, st, a0);
+        if (take_launch_timing(a, b)) hipExtLaunchKernelGGL((k_fps_dct_div_r<LOGN, PROF>), grid, dim3(T), lds, st, a, b, 0, a0);
+        else hipLaunchKernelGGL((k_fps_dct_div_r<LOGN, PROF>), grid, dim3(T), lds, st, a0);
         return (int)grid.x;
     }
     return -1;
 }
 
-template <int LOGN>
+template <int LOGN, bool PROF = false>
 int div_pair(const Knobs& k, const FpsDivArgs& a0, hipStream_t st) {
     constexpr int T = Fft<LOGN>::T;
     const size_t lds = sizeof(cplx) * (size_t)FftLds<LOGN>::n;
-    lds_attr_once((const void*)k_fps_dct_div<LOGN>, (int)lds);
+    lds_attr_once((const void*)k_fps_dct_div<LOGN, PROF>, (int)lds);
     const dim3 grid(std::min(a0.cnt, k.fps_grid > 0 ? k.fps_grid : 1 << 30));   // (as dct_pair)
     hipEvent_t a, b;
-    if (take_launch_timing(a, b)) hipExtLaunchKernelGGL(k_fps_dct_div<LOGN>, grid, dim3(T), lds, st, a, b, 0, a0);
-    else hipLaunchKernelGGL(k_fps_dct_div<LOGN>, grid, dim3(T), lds, st, a0);
+    if (take_launch_timing(a, b)) hipExtLaunchKernelGGL((k_fps_dct_div<LOGN, PROF>), grid, dim3(T), lds, st, a, b, 0, a0);
+    else hipLaunchKernelGGL((k_fps_dct_div<LOGN, PROF>), grid, dim3(T), lds, st, a0);
     return (int)grid.x;
 }
 
@@ -2492,15 +2497,17 @@ int launch_fps_div(const Knobs& k, const Geo& g, const Coef& c, double dt, const
         a.pstep = std::max(np - 1, 1);
     }
     const int lg = g.ny == (1 << 14) ? 14 : fps_log2(g.ny);
+    const bool prof = g.pt[0] || g.pt[1] || g.pt[2] || g.pt[3];
     if (fps_div_real(k, lg, outE)) {   // (per-row sums: 2 np partials)
         if (a.cnt <= 0) return 2 * np;
         int n = -1;
+        // (prof: a side carries an edge profile -- the instantiations that read the tables)
         switch (lg) {
-        case 10: n = div_row<10>(a, st); break;
-        case 11: n = div_row<11>(a, st); break;
-        case 12: n = div_row<12>(a, st); break;
-        case 13: n = div_row<13>(a, st); break;
-        case 14: n = div_row<14>(a, st); break;   // (ny = 16384: 128 KiB, one workgroup of 1024 threads per CU)
+        case 10: n = prof ? div_row<10, true>(a, st) : div_row<10>(a, st); break;
+        case 11: n = prof ? div_row<11, true>(a, st) : div_row<11>(a, st); break;
+        case 12: n = prof ? div_row<12, true>(a, st) : div_row<12>(a, st); break;
+        case 13: n = prof ? div_row<13, true>(a, st) : div_row<13>(a, st); break;
+        case 14: n = prof ? div_row<14, true>(a, st) : div_row<14>(a, st); break;   // (ny = 16384: 128 KiB, one workgroup of 1024 threads per CU)
         default: return -1;
         }
         return n < 0 ? -1 : 2 * np;
@@ -2508,16 +2515,16 @@ int launch_fps_div(const Knobs& k, const Geo& g, const Coef& c, double dt, const
     if (a.cnt <= 0) return np;
     int n = -1;
     switch (lg) {
-    case 4: n = div_pair<4>(k, a, st); break;
-    case 5: n = div_pair<5>(k, a, st); break;
-    case 6: n = div_pair<6>(k, a, st); break;
-    case 7: n = div_pair<7>(k, a, st); break;
-    case 8: n = div_pair<8>(k, a, st); break;
-    case 9: n = div_pair<9>(k, a, st); break;
-    case 10: n = div_pair<10>(k, a, st); break;
-    case 11: n = div_pair<11>(k, a, st); break;
-    case 12: n = div_pair<12>(k, a, st); break;
-    case 13: n = div_pair<13>(k, a, st); break;
+    case 4: n = prof ? div_pair<4, true>(k, a, st) : div_pair<4>(k, a, st); break;
+    case 5: n = prof ? div_pair<5, true>(k, a, st) : div_pair<5>(k, a, st); break;
+    case 6: n = prof ? div_pair<6, true>(k, a, st) : div_pair<6>(k, a, st); break;
+    case 7: n = prof ? div_pair<7, true>(k, a, st) : div_pair<7>(k, a, st); break;
+    case 8: n = prof ? div_pair<8, true>(k, a, st) : div_pair<8>(k, a, st); break;
+    case 9: n = prof ? div_pair<9, true>(k, a, st) : div_pair<9>(k, a, st); break;
+    case 10: n = prof ? div_pair<10, true>(k, a, st) : div_pair<10>(k, a, st); break;
+    case 11: n = prof ? div_pair<11, true>(k, a, st) : div_pair<11>(k, a, st); break;
+    case 12: n = prof ? div_pair<12, true>(k, a, st) : div_pair<12>(k, a, st); break;
+    case 13: n = prof ? div_pair<13, true>(k, a, st) : div_pair<13>(k, a, st); break;
     default: return -1;
     }
     return n < 0 ? -1 : np;

@@ -41,7 +41,19 @@ struct EdgeDev {
     int neu;            // NEUMANN outflow (velocity ghost q, phi ghost 2.5/-2/0.5)
     int enx, eny;       // outward normal
     double c0, c1;      // velocity ghost constants (u, v) of walls / inlets
+    // edge profile (ns_edge_profile): the constant of component pd per boundary face instead, 2 info(k) at k = the
+    // face's column j (x-normal edge, ny entries) or global row i (y-normal edge, nx entries); null: uniform
+    const double* pt = nullptr;
+    int pd = 0;
 };
+// the ghost constant of component d across a face at table index k of n: the edge's own (c0, c1), or its profile's
+// entry.  The index is clamped: callers evaluate the ghost and then select, so the read also runs for cells that
+// have no such face (staged and clamped cells, the deep ghost rows of multi-rank launches)
+__host__ __device__ inline double edge_const(double c0, double c1, const double* pt, int pd, int d, int k, int n) {
+    double cc = d == 0 ? c0 : c1;
+    if (pt && pd == d) cc = pt[k < 0 ? 0 : k < n ? k : n - 1];
+    return cc;
+}
 
 // Geometry of one x-slab.  Fields are (nxl + 2*HALO) rows of ld doubles, j contiguous;
 // pointers handed to kernels point at local row 0.  Global row = i0 + local row.
@@ -56,6 +68,9 @@ struct Geo {
     int neu[4];
     double c0[4], c1[4];
     int enx[4], eny[4];  // outward normal of the edge on that side
+    // edge profiles of the rectangle's sides (EdgeDev::pt / pd; W, E: ny entries, S, N: nx entries); null: uniform
+    const double* pt[4] = {nullptr, nullptr, nullptr, nullptr};
+    int pd[4] = {0, 0, 0, 0};
     // (r5) the rows whose values enter a launch's reductions (residual / norm / min-max partials), in
     // this geometry's local rows: a launch that also computes rows of the neighbours' slabs -- the deep
     // ghost rows of multi-rank steps (ns_solver.cpp deep_geo) -- sums only its own slab's rows

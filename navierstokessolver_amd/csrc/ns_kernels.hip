@@ -63,8 +63,14 @@ __device__ __forceinline__ double ldf(const double* f, int ld, int li, int j) {
 
 // velocity ghost, EvaluateGhostStencil_V (FluidSolver.cpp:166-173):
 //   walls / inlets: weights {-1} + constant[d];  NEUMANN: weights {1}
-__device__ __forceinline__ double ghost_v(const Geo& g, double q, int side, int d) {
-    return g.neu[side] ? q : (-q + (d == 0 ? g.c0[side] : g.c1[side]));
+// k: the face's index along its side (column j on W / E, global row i on S / N), where an edge profile is read
+// (edge_const; PROF false: the side's own constant, no table test -- the unprofiled instantiations of the kernels
+// that evaluate a ghost for every cell)
+template <bool PROF = true>
+__device__ __forceinline__ double ghost_v(const Geo& g, double q, int side, int d, int k) {
+    const double cc = PROF ? edge_const(g.c0[side], g.c1[side], g.pt[side], g.pd[side], d, k, side < 2 ? g.ny : g.nx)
+                           : (d == 0 ? g.c0[side] : g.c1[side]);
+    return g.neu[side] ? q : (-q + cc);
 }
 
 // minmode (FluidSolver.cpp:671-674)
@@ -141,19 +147,31 @@ __device__ __forceinline__ void block_reduce_min(double (&x)[NV], double* out) {
 // TopoRect folds to bound checks on the compile-time offsets and per-side constants (the
 // rectangle kernels compile to what they were); TopoMask reads the int32 topology plane
 // (FC_*) and the edge table of a non-rectangular domain.
-struct TopoRect {
+// PROF false: the sides' own constants only, no edge-profile test (K1's ring in the kernels a solver without profiles
+// launches: the code they had before profiles existed)
+template <bool PROF>
+struct TopoRectT {
     const Geo& g;
     int gi, j;
-    __device__ __forceinline__ TopoRect(const Geo& g_, int li, int j_) : g(g_), gi(g_.i0 + li), j(j_) {}
+    __device__ __forceinline__ TopoRectT(const Geo& g_, int li, int j_) : g(g_), gi(g_.i0 + li), j(j_) {}
     __device__ __forceinline__ bool cell() const { return true; }
     __device__ __forceinline__ bool in(int di, int dj) const {
         if (dj == 0) return di < 0 ? gi + di >= 0 : gi + di < g.nx;
         if (di == 0) return dj < 0 ? j + dj >= 0 : j + dj < g.ny;
         return gi + di >= 0 && gi + di < g.nx && j + dj >= 0 && j + dj < g.ny;
     }
-    __device__ __forceinline__ double gv(int, int, int k, double q, int d) const { return ghost_v(g, q, k, d); }
-    __device__ __forceinline__ EdgeDev edge(int k) const { return EdgeDev{g.neu[k], g.enx[k], g.eny[k], g.c0[k], g.c1[k]}; }
+    __device__ __forceinline__ double gv(int di, int dj, int k, double q, int d) const {
+        return ghost_v<PROF>(g, q, k, d, k < 2 ? j + dj : gi + di);
+    }
+    // (the constants resolved at this cell's own face: rhs_bc's wall terms)
+    __device__ __forceinline__ EdgeDev edge(int k) const {
+        if (!PROF) return EdgeDev{g.neu[k], g.enx[k], g.eny[k], g.c0[k], g.c1[k]};
+        const int f = k < 2 ? j : gi, n = k < 2 ? g.ny : g.nx;
+        return EdgeDev{g.neu[k], g.enx[k], g.eny[k], edge_const(g.c0[k], g.c1[k], g.pt[k], g.pd[k], 0, f, n),
+                       edge_const(g.c0[k], g.c1[k], g.pt[k], g.pd[k], 1, f, n)};
+    }
 };
+using TopoRect = TopoRectT<true>;
 // a cell at least two cells from every wall (the MUSCL stencil's reach): every neighbour exists,
 // no ghost is evaluated -- K1's interior tiles (k_rhs_lds) skip the existence selects
 struct TopoInner {
@@ -180,9 +198,14 @@ struct TopoMask {
     }
     __device__ __forceinline__ double gv(int di, int dj, int k, double q, int d) const {
         const EdgeDev& E = g.et[fc_edge(di == 0 && dj == 0 ? code : at(di, dj), k)];
-        return E.neu ? q : (-q + (d == 0 ? E.c0 : E.c1));
+        return E.neu ? q : (-q + edge_const(E.c0, E.c1, E.pt, E.pd, d, k < 2 ? j + dj : g.i0 + li + di, k < 2 ? g.ny : g.nx));
     }
-    __device__ __forceinline__ EdgeDev edge(int k) const { return g.et[fc_edge(code, k)]; }
+    __device__ __forceinline__ EdgeDev edge(int k) const {
+        const EdgeDev& E = g.et[fc_edge(code, k)];
+        const int f = k < 2 ? j : g.i0 + li, n = k < 2 ? g.ny : g.nx;
+        return EdgeDev{E.neu, E.enx, E.eny, edge_const(E.c0, E.c1, E.pt, E.pd, 0, f, n),
+                       edge_const(E.c0, E.c1, E.pt, E.pd, 1, f, n)};
+    }
 };
 
 // ------------------------------------------------ grad phi (GradP, FluidSolver.cpp:420-456)
@@ -1561,7 +1584,7 @@ struct RhsStreamArgs {
     // go to uo, vo and their min / max to mm (4 per strip, then 4 per ring block)
     double *uo, *vo, *mm;
 };
-template <bool CORR = false>
+template <bool CORR = false, bool PROF = true>
 __device__ __forceinline__ void rhs_ring_body(const Geo& g, const Coef& c, double dt, double re,
                                               const double* __restrict__ u, const double* __restrict__ v,
                                               const double* __restrict__ phi, double* __restrict__ cu,
@@ -1593,7 +1616,7 @@ __device__ __forceinline__ void rhs_ring_body(const Geo& g, const Coef& c, doubl
         auto X = [&](int t, int d) { return (t == 0 ? c.hx : t == 1 ? c.rhx : c.rsx)[gi + d]; };
         auto Y = [&](int t, int d) { return (t == 0 ? c.hy : t == 1 ? c.rhy : c.rsy)[j + d]; };
         double cun, cvn, ru_, rv_;
-        rhs_cell<true, TopoRect>(g, c, dt, re, U, V, X, Y, phi, li, j, cu[o], cv[o], cun, cvn, ru_, rv_);
+        rhs_cell<true, TopoRectT<PROF>>(g, c, dt, re, U, V, X, Y, phi, li, j, cu[o], cv[o], cun, cvn, ru_, rv_);
         cu[o] = cun;
         cv[o] = cvn;
         ru[o] = ru_;
@@ -1630,7 +1653,7 @@ constexpr int K1_LMAX = 128;      // k_rhs_s: rows per strip at most (one reside
 #define K1_ESPLIT 4               // (r5) k_rhs_s: rows per run of the edge bands after a slab's exchange (0: one run)
 #endif
 constexpr int RC_K1 = 4;          // k_rhs_s: row tables from row ib-4 (the window-fill steps read ib-4 .. )
-template <bool NT, int SK, bool UY = false, bool CORR = false>
+template <bool NT, int SK, bool UY = false, bool CORR = false, bool PROF = false>
 __device__ __forceinline__ void rhs_s_body(const RhsStreamArgs& A) {
     const Geo& g = A.g;
     const Coef& c = A.c;
@@ -1638,7 +1661,7 @@ __device__ __forceinline__ void rhs_s_body(const RhsStreamArgs& A) {
     // 12 us slower, 305.5 vs 293.3 us on one box -- they then hold resident slots the strips' one round needs;
     // without the ring -- a timing probe, wrong results -- K1' took 331 vs 338 us: the ring is ~7 us of it)
     if ((int)blockIdx.x >= A.nsblk) {
-        rhs_ring_body<CORR>(g, c, A.dt, A.re, A.u, A.v, A.phi, A.cu, A.cv, A.ru, A.rv, A.part + 2 * A.nstr, A.R,
+        rhs_ring_body<CORR, PROF>(g, c, A.dt, A.re, A.u, A.v, A.phi, A.cu, A.cv, A.ru, A.rv, A.part + 2 * A.nstr, A.R,
                             (int)blockIdx.x - A.nsblk, A.uo, A.vo, CORR ? A.mm + 4 * A.nstr : nullptr);
         return;
     }
@@ -1918,6 +1941,11 @@ __global__ __launch_bounds__(256) void k_rhs_s(RhsStreamArgs A) { rhs_s_body<NT,
 // (r6) K1 with the previous step's K5 folded in (CORR)
 template <bool NT, int SK>
 __global__ __launch_bounds__(256) void k_rhs_sc(RhsStreamArgs A) { rhs_s_body<NT, SK, false, true>(A); }
+// a side carries an edge profile (PROF): the same strips, the ring reading the tables
+template <bool NT, int SK>
+__global__ __launch_bounds__(256) void k_rhs_sp(RhsStreamArgs A) { rhs_s_body<NT, SK, false, false, true>(A); }
+template <bool NT, int SK>
+__global__ __launch_bounds__(256) void k_rhs_scp(RhsStreamArgs A) { rhs_s_body<NT, SK, false, true, true>(A); }
 template <bool NT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k_rhs_s3(RhsStreamArgs A) {
     rhs_s_body<NT, 2>(A);
@@ -2445,7 +2473,8 @@ __device__ __forceinline__ double extrap_comb(double a, double x, double b, doub
 #ifndef K6_SD
 #define K6_SD 2
 #endif
-template <int K>   // 3: divergence, 5: correction, 6: correction + the next Poisson guess, 7: Poisson apply
+// PROF (K3 only): a side carries an edge profile -- the unprofiled instantiation reads no table
+template <int K, bool PROF = false>
 __global__ __launch_bounds__(256) void k_cell_s(CellStreamArgs A) {
     const Geo& g = A.g;
     const Coef& c = A.c;
@@ -2524,10 +2553,11 @@ __global__ __launch_bounds__(256) void k_cell_s(CellStreamArgs A) {
                 for (int e = 0; e < 2; e++) {
                     const double uc = e ? W1.y : W1.x, uw = e ? W0.y : W0.x, ue = e ? W2.y : W2.x;
                     const double vc = e ? vv.y : vv.x, vs = e ? vv.x : vs0, vn = e ? vn1 : vv.y;
-                    const double V0 = face_val(uc, uw, hW, fw, ghost_v(g, uc, 0, 0));
-                    const double V1 = face_val(uc, ue, hE, fe, ghost_v(g, uc, 1, 0));
-                    const double V2 = face_val(vc, vs, e ? s1 : s0, e ? fs1 : fs0, ghost_v(g, vc, 2, 1));
-                    const double V3 = face_val(vc, vn, e ? n1 : n0, e ? fn1 : fn0, ghost_v(g, vc, 3, 1));
+                    const int kj = e ? k1 : k0;
+                    const double V0 = face_val(uc, uw, hW, fw, ghost_v<PROF>(g, uc, 0, 0, kj));
+                    const double V1 = face_val(uc, ue, hE, fe, ghost_v<PROF>(g, uc, 1, 0, kj));
+                    const double V2 = face_val(vc, vs, e ? s1 : s0, e ? fs1 : fs0, ghost_v<PROF>(g, vc, 2, 1, gi));
+                    const double V3 = face_val(vc, vn, e ? n1 : n0, e ? fn1 : fn0, ghost_v<PROF>(g, vc, 3, 1, gi));
                     val[e] = ((V1 - V0) / hx + (V3 - V2) / (e ? hy1 : hy0)) / A.dt;
                 }
                 if (wr) {   // (an odd ny's last pair: column ny is row padding, left untouched)
@@ -5326,6 +5356,7 @@ static hipError_t launch_raw(const void* k, dim3 grid, dim3 block, void** args, 
 }
 
 static long resident_waves(const Knobs& kn, const void* k);
+static bool geo_profiled(const Geo& g) { return g.pt[0] || g.pt[1] || g.pt[2] || g.pt[3]; }
 static int strip_rows(int nxl, long nsj, long cap, int lmin, int lmax = 64);
 
 int launch_rhs(const Knobs& kn, const Geo& g, const Coef& c, double dt, double re, const double* u, const double* v,
@@ -5379,6 +5410,9 @@ int launch_rhs(const Knobs& kn, const Geo& g, const Coef& c, double dt, double r
             // the fewest rows that keep every strip in ONE resident round (strip_rows caps at 64:
             // 4096^2 at 2 waves / SIMD then left 128 of 2176 strips to a second round)
             const long nsi = std::max(1L, resident_waves(kn, kk) / A.nsj);
+            // (an edge profile: the default kernels' profiled forms, on the strips planned for the unprofiled one --
+            // the partials' grouping, and so every sum, stays what it is without a profile)
+            if (geo_profiled(g)) kk = uo ? (const void*)k_rhs_scp<true, 2> : (const void*)k_rhs_sp<true, 2>;
             int L = std::min(std::max((int)((g.nxl + nsi - 1) / nsi + 1) & ~1, 8), K1_LMAX);
             // (r6, A/B) NSGPU_K1_L: rows per strip (several resident rounds of shorter strips)
             if (kn.k1_l >= 4) L = std::min(kn.k1_l & ~1, K1_LMAX);
@@ -5518,7 +5552,12 @@ static int launch_cell_s(const Knobs& kn, CellStreamArgs A, hipStream_t st) {
     } else {
         nstr = A.nsj * plan_rows(A.g.nxl, L, 1, &A.P);   // window rows ib-1 .. ie
     }
-    if (A.P.nrun > 0) NS_LAUNCH(k_cell_s<K>, dim3((A.nsj * A.P.nrun + 3) / 4), dim3(256), 0, st, A);
+    // (K3 with an edge profile: the same strips -- L from the unprofiled kernel's residency -- through the instantiation
+    // that reads the tables)
+    if (A.P.nrun > 0) {
+        if (K == 3 && geo_profiled(A.g)) NS_LAUNCH((k_cell_s<3, true>), dim3((A.nsj * A.P.nrun + 3) / 4), dim3(256), 0, st, A);
+        else NS_LAUNCH(k_cell_s<K>, dim3((A.nsj * A.P.nrun + 3) / 4), dim3(256), 0, st, A);
+    }
     return nstr;
 }
 

@@ -235,6 +235,16 @@ struct ns_solver {
     int mband_n = 0;
     int32_t* ecell_mem = nullptr;   // (r5) masked domain: the slab's domain cells that are not FC_DEEP (g.ecell)
     nsg::EdgeDev* et_mem = nullptr;
+    std::vector<nsg::EdgeDev> et_host;   // ... and its host copy (re-uploaded when an edge's profile pointer changes)
+    // edge profiles (ns_edge_profile): per edge its type and normal, the rectangle side it covers (-1 on a masked
+    // domain) and the device table of 2 info(k) with its host copy (ny entries for an x-normal edge, nx for a y-normal
+    // one; allocated on first use)
+    struct EdgeProf {
+        int type = 0, enx = 0, eny = 0, side = -1;
+        std::vector<double> host;
+        double* tab = nullptr;
+    };
+    std::vector<EdgeProf> eprof;
     ns_host_transport ht{};      // host transport (ht.exchange != NULL) instead of RCCL
     double* stage = nullptr;     // pinned staging for the host transport
     size_t stage_n = 0;
@@ -3819,7 +3829,8 @@ int edge_dev(const ns_grid_desc* gd, const ns_params* p, int e, nsg::EdgeDev* D)
         }
     } else {
         set_err("edge %d: boundary condition type %d is not supported (INLET_PARABOLIC / PRESSURE / unset "
-                "have no ghost stencil in the reference)", e, E.type);
+                "have no ghost stencil in the reference; a parabolic inlet is an INLET_UNI edge with "
+                "ns_parabolic_profile's values as its ns_edge_profile)", e, E.type);
         return NS_EINVAL;
     }
     return 0;
@@ -3970,6 +3981,12 @@ int host_geometry(ns_solver* s, const ns_grid_desc* gd, const ns_params* p, Host
             return NS_EINVAL;
         }
     }
+    s->eprof.assign(gd->n_edges, ns_solver::EdgeProf{});
+    for (int e = 0; e < gd->n_edges; e++) {
+        s->eprof[e].type = gd->edges[e].type;
+        s->eprof[e].enx = gd->edges[e].nx;
+        s->eprof[e].eny = gd->edges[e].ny;
+    }
     if (!masked) {
         // sides from edge normals (a rectangle: Grid.cpp:35-63 gives one edge per side)
         const int snx[4] = {-1, 1, 0, 0}, sny[4] = {0, 0, -1, 1};
@@ -3985,6 +4002,7 @@ int host_geometry(ns_solver* s, const ns_grid_desc* gd, const ns_params* p, Host
         for (int k = 0; k < 4; k++) {
             if (side_edge[k] < 0) { set_err("side %d has no edge: not a rectangle", k); return NS_EINVAL; }
             s->side_edge[k] = side_edge[k];
+            s->eprof[side_edge[k]].side = k;
             nsg::EdgeDev D;
             if (int rc = edge_dev(gd, p, side_edge[k], &D)) return rc;
             g.enx[k] = D.enx;
@@ -4308,6 +4326,7 @@ int create_fields(ns_solver* s, const HostGeo& H) {
     if (etd.size() < 32) etd.resize(32, nsg::EdgeDev{});
     CHK(dev_upload(s, &s->fc_mem, H.fch, "topology"));
     CHK(dev_upload(s, &s->et_mem, etd, "topology"));
+    s->et_host = etd;
     s->g.fc = s->fc_mem + (size_t)nsg::HALO * g.ld;
     s->g.et = s->et_mem;
     if (!H.mband.empty()) {
@@ -4437,6 +4456,32 @@ int64_t ns_device_bytes(int32_t nxl, int32_t ny) {
     return (int64_t)NS_NUM_ARR * (nxl + 2 * nsg::HALO) * ld * 8;
 }
 
+// one edge's profile onto the device: info[k] per face (the table holds 2 info(k), the ghost constant edge_dev derives
+// from info), or null: back to the edge's uniform constant.  Ordered on the solver's stream, then waited for
+static int edge_profile_apply(ns_solver* s, int e, const double* info) {
+    ns_solver::EdgeProf& P = s->eprof[e];
+    const int n = P.enx != 0 ? s->g.ny : s->g.nx;
+    if (info) {
+        if (!P.tab) CHK(dev_alloc(s, &P.tab, (size_t)n * sizeof(double), false, "edge profile"));
+        P.host.resize(n);
+        for (int k = 0; k < n; k++) P.host[k] = 2 * info[k];
+        HIPCHK(hipMemcpyAsync(P.tab, P.host.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, s->st));
+    }
+    const double* pt = info ? P.tab : nullptr;
+    // the component edge_dev puts the constant in: an inlet's normal one, a wall's tangential one
+    const int pd = (P.type == NS_BC_WALL) == (P.enx != 0) ? 1 : 0;
+    if (P.side >= 0) {
+        s->g.pt[P.side] = pt;
+        s->g.pd[P.side] = pd;
+    } else if (s->et_host[e].pt != pt || s->et_host[e].pd != pd) {
+        s->et_host[e].pt = pt;
+        s->et_host[e].pd = pd;
+        HIPCHK(hipMemcpyAsync(s->et_mem + e, &s->et_host[e], sizeof(nsg::EdgeDev), hipMemcpyHostToDevice, s->st));
+    }
+    HIPCHK(hipStreamSynchronize(s->st));
+    return 0;
+}
+
 int ns_create(const ns_grid_desc* gd, const ns_params* p, ns_solver** out) {
     if (!gd || !p || !out) { set_err("null argument"); return NS_EINVAL; }
     *out = nullptr;
@@ -4461,6 +4506,58 @@ int ns_create(const ns_grid_desc* gd, const ns_params* p, ns_solver** out) {
         return rc;
     }
     *out = s;
+    return 0;
+}
+
+int ns_edge_profile(ns_solver* s, int32_t edge, const double* info, int32_t n) {
+    if (!s) { set_err("null argument"); return NS_EINVAL; }
+    if (edge < 0 || edge >= (int)s->eprof.size()) {
+        set_err("ns_edge_profile: edge %d of a grid with %d edges", edge, (int)s->eprof.size());
+        return NS_EINVAL;
+    }
+    const ns_solver::EdgeProf& P = s->eprof[edge];
+    if (P.type == NS_BC_NEUMANN) {
+        set_err("ns_edge_profile: edge %d is a NEUMANN edge: it has no boundary value", edge);
+        return NS_EINVAL;
+    }
+    const int want = P.enx != 0 ? s->g.ny : s->g.nx;
+    if (n != want) {
+        set_err("ns_edge_profile: edge %d: %d values for an extent of %d faces (%s of the whole grid)", edge, n, want,
+                P.enx != 0 ? "ny" : "nx");
+        return NS_EINVAL;
+    }
+    if (info)
+        for (int k = 0; k < n; k++)
+            if (!std::isfinite(info[k])) {
+                set_err("ns_edge_profile: edge %d: info[%d] is not finite", edge, k);
+                return NS_EINVAL;
+            }
+    HIPCHK(hipSetDevice(s->device));
+    return edge_profile_apply(s, edge, info);
+}
+
+int ns_parabolic_profile(const double* h, int32_t n, int32_t k0, int32_t k1, double mean, double* out) {
+    if (!h || !out) { set_err("ns_parabolic_profile: null argument"); return NS_EINVAL; }
+    if (n <= 0 || k0 < 0 || k1 > n || k0 >= k1) {
+        set_err("ns_parabolic_profile: faces [%d, %d) of %d", k0, k1, n);
+        return NS_EINVAL;
+    }
+    if (!std::isfinite(mean)) { set_err("ns_parabolic_profile: the mean is not finite"); return NS_EINVAL; }
+    // (the face positions in long double: a face's sb is the next one's sa, so sum out[k] h[k] telescopes to mean L
+    // up to the rounding of each term, not of the running position)
+    long double L = 0.0L;
+    for (int k = k0; k < k1; k++) {
+        if (!(h[k] > 0) || !std::isfinite(h[k])) { set_err("ns_parabolic_profile: h[%d] = %g is not positive", k, h[k]); return NS_EINVAL; }
+        L += h[k];
+    }
+    for (int k = 0; k < n; k++) out[k] = 0.0;
+    // the face average of 6 s (1 - s) over [sa, sb]: 3 (sa + sb) - 2 (sa^2 + sa sb + sb^2)
+    long double x = 0.0L;
+    for (int k = k0; k < k1; k++) {
+        const long double sa = x / L, sb = k + 1 == k1 ? 1.0L : (x + h[k]) / L;
+        out[k] = (double)(mean * (3.0L * (sa + sb) - 2.0L * (sa * sa + sa * sb + sb * sb)));
+        x += h[k];
+    }
     return 0;
 }
 
@@ -4507,6 +4604,8 @@ void ns_destroy(ns_solver* s) {
     if (s->mband_tiles) (void)hipFree(s->mband_tiles);
     if (s->ecell_mem) (void)hipFree(s->ecell_mem);
     if (s->et_mem) (void)hipFree(s->et_mem);
+    for (auto& e : s->eprof)
+        if (e.tab) (void)hipFree(e.tab);
     if (s->ksc) (void)hipFree(s->ksc);
     if (s->coef) (void)hipFree(s->coef);
     if (s->part) (void)hipFree(s->part);

@@ -175,6 +175,20 @@ class GpuSolver:
                 raise ValueError(f"compact field of {a.size} values; this slab holds {n} cells")
         L.check(L.lib().ns_set_fields(self._h, *[None if a is None else _dptr(a) for a in keep]))
 
+    # ---- boundary values that vary along an edge (ns_edge_profile)
+    def set_edge_profile(self, edge: int, info) -> None:
+        """Per-face bcInfo of one WALL / INLET_UNI edge (the grid's edge order): info[k] at k = the face's column j
+        for an x-normal edge (ny values) or its global row i for a y-normal edge (nx values of the whole grid, on
+        every rank); entries where the edge has no face are ignored.  Between steps, any number of times."""
+        a = np.ascontiguousarray(np.asarray(info, dtype=np.float64).ravel())
+        L.check(L.lib().ns_edge_profile(self._h, int(edge), _dptr(a), a.size))
+
+    def clear_edge_profile(self, edge: int) -> None:
+        """Back to the edge's own value (its info)."""
+        e = self.grid.edges[edge] if 0 <= int(edge) < len(self.grid.edges) else None
+        n = 0 if e is None else (self.grid.ny if e.nx != 0 else self.grid.nx)
+        L.check(L.lib().ns_edge_profile(self._h, int(edge), None, n))
+
     # ---- passive scalar (ns_scalar_*: one rank's rectangle)
     def enable_scalar(self, pe: float, bc) -> None:
         """A scalar T carried by the step, Peclet number pe.  bc: one ("dirichlet", value) or ("zerograd",)
