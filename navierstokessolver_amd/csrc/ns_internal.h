@@ -196,6 +196,18 @@ void time_next_launch(hipEvent_t a, hipEvent_t b);
 bool time_next_launch_pending();
 // a launcher outside ns_kernels.hip takes the pending request (and stamps its launch with a, b)
 bool take_launch_timing(hipEvent_t& a, hipEvent_t& b);
+// the event calls of the kernel-timing recorder (ns_timing.h's Api): HIP events, the dispatch stamp above
+struct HipTiming {
+    using Event = hipEvent_t;
+    using Stream = hipStream_t;
+    static int create(Event* e) { return hipEventCreate(e); }
+    static int destroy(Event e) { return hipEventDestroy(e); }
+    static int record(Event e, Stream st) { return hipEventRecord(e, st); }
+    static int wait(Event e) { return hipEventSynchronize(e); }
+    static int elapsed(float* ms, Event a, Event b) { return hipEventElapsedTime(ms, a, b); }
+    static void arm(Event a, Event b) { time_next_launch(a, b); }
+    static bool disarm() { return time_next_launch_pending(); }   // (true: no launch had taken the stamp)
+};
 // strip subset of the following two-sweep pass launches (k_sweep2): 0 all, 1 the strips
 // whose read cone lies inside the slab, 2 the others (exchange / compute overlap)
 void set_strip_phase(int phase);

@@ -26,6 +26,7 @@
 
 #include "../../include/nsgpu.h"
 #include "ns_internal.h"
+#include "ns_timing.h"
 
 namespace {
 
@@ -86,6 +87,10 @@ enum {
 };
 constexpr int BUS_NV = 10, BUS_NSUM = 6;
 
+// the step's kernel timings: the recorder of ns_timing.h over HIP events (nsg::HipTiming)
+using Timing = nsg::Timing<nsg::HipTiming>;
+#define TCHK(x) HIPCHK(static_cast<hipError_t>(x))
+
 }  // namespace
 
 // one multigrid level (level 0 = the solver's own PHI / TMP / RPHI arrays)
@@ -136,11 +141,11 @@ struct ns_solver {
     int rank = 0, nranks = 1;
     ncclComm_t comm = nullptr;
     double ncells = 0;           // global cell count
-    std::vector<hipEvent_t> ev;  // timing events (pairs)
-    std::vector<char> evtag;     // per pair: 0 = sweep / prolongation pass, 1 = restriction pass
-    std::vector<hipEvent_t> hev; // Helmholtz pass timing events (pairs; timing == 1, single rank)
-    int hn = 0;                  // Helmholtz pairs recorded this step
-    std::vector<int> hcomp;      // components per recorded Helmholtz launch (2: the one-rank two-field pass)
+    // timed steps (timing == 1): every timed kernel call is an interval of this recorder, by kind (ns_timing.h) --
+    // drained where a host sync has passed them: the multigrid's at each residual check, the Helmholtz passes', K1's
+    // and the wall bands' after helm_solve, K5's at the next host sync (the next step's, after ns_step_async), the
+    // direct solve's after waiting for its own last event, the scalar's in scalar_end
+    Timing tm;
     int helm_batch0 = 4, pois_batch0 = 8;
     int helm_next = 4;           // first Helmholtz batch of the next step (adaptive unless check_every)
     int helm_adapt = 1;
@@ -215,7 +220,6 @@ struct ns_solver {
     int cv_n = 0, cv_dn = 0;
     double* ksc = nullptr;
     bool pc_active = false;      // inside mg_precond: level 0 has no mean shift
-    bool pc_timing = false;      // ... and its level-0 passes are timed (the outflow Poisson solve)
     bool krylov_mg = false;      // the Poisson BiCGStab is preconditioned by a V-cycle (else Jacobi)
     // the outflow preconditioner: a rectangle whose only NEUMANN side is W (0) or
     // E (1): the V-cycle's hierarchy closes that side with a Dirichlet-centre ghost whose data,
@@ -352,10 +356,6 @@ struct ns_solver {
     // steps the divergence goes straight into the transformed plane, rhs_phi is stored only for a checked
     // solve; fps_pre: the plane holds this step's coefficients (pois_solve_fps skips its DCT)
     bool fps_fuse = true, fps_pre = false, fps_pre_b = false;
-    // timed steps: K1 (kev[0..1]) and the direct solve's transforms / recurrences (kev[2..7]); (r6) the wall-band
-    // launches (kev[8..11], two launches) and K5 (kev[12..13], read at the next host sync: k5_pend)
-    hipEvent_t kev[14] = {};
-    int band_timed = 0, k5_pend = 0;
     // (r6) the deferred correction: an ns_step_async step ends after its Poisson solve (U, V = u*, v*, PHI = phi^n)
     // and the next step's K1 applies CorrectVelocities on the fly (k_rhs_sc: K5 folded into K1 -- one HBM pass
     // of 40 B/cell less); any other entry point that reads or writes the fields runs K5 first (materialize)
@@ -379,10 +379,10 @@ struct ns_solver {
         double* bxy = nullptr;
         nsg::Coef ct{};
         double *part = nullptr, *scal = nullptr, *hs = nullptr;
-        hipEvent_t ev = nullptr, kev[2] = {nullptr, nullptr};
+        hipEvent_t ev = nullptr;
         // the step's first batch of sweeps is what the previous step needed; it is enqueued, with its residual and
         // the min / max of its result, before the velocities' Helmholtz solve, whose residual check brings them
-        int next = 4, ok_steps = 0, sweeps = 0, timed = 0;
+        int next = 4, ok_steps = 0, sweeps = 0;
         ns_scalar_stats last{};
         // Boussinesq buoyancy (ns_scalar_buoyancy): f = (bx, by) (T - tref), applied by k_rhs_t's buoyant variant
         double bx = 0.0, by = 0.0, tref = 0.0;
@@ -600,108 +600,20 @@ int fetch_end(ns_solver* s) {
 }
 int extrapolate_phi(ns_solver* s);
 
-// A timed kernel call.  One rank: the call is a single launch, timed by the dispatch's own
-// begin / end stamps (hipExtLaunchKernel's events: the interval rocprofv3's kernel trace
-// reports).  Multi-rank calls (exchanges, split launches) and NSGPU_EXT_TIMING=0: marker
-// events around the call, which also count the launch's dispatch latency.
-int t_begin(ns_solver* s, hipEvent_t a, hipEvent_t b) {
-    if (s->nranks == 1 && s->k.ext_timing) {
-        nsg::time_next_launch(a, b);
-        return 0;
-    }
-    HIPCHK(hipEventRecord(a, s->st));
-    return 0;
-}
-int t_end(ns_solver* s, hipEvent_t a, hipEvent_t b) {
-    if (s->nranks == 1 && s->k.ext_timing) {
-        if (nsg::time_next_launch_pending()) {   // the call launched no kernel: an empty interval
-            HIPCHK(hipEventRecord(a, s->st));
-            HIPCHK(hipEventRecord(b, s->st));
-        }
-        return 0;
-    }
-    HIPCHK(hipEventRecord(b, s->st));
-    return 0;
-}
-int ensure_kev(ns_solver* s) {
-    for (auto& e : s->kev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    return 0;
-}
-float kev_ms(ns_solver* s, int k) {
-    float ms = 0.f;
-    return hipEventElapsedTime(&ms, s->kev[k], s->kev[k + 1]) == hipSuccess ? ms : 0.f;
-}
-int ensure_events(ns_solver* s, size_t n) {
-    while (s->ev.size() < n) {
-        hipEvent_t e;
-        HIPCHK(hipEventCreate(&e));
-        s->ev.push_back(e);
-    }
-    if (s->evtag.size() < n / 2 + 1) s->evtag.resize(n / 2 + 1, 0);
-    return 0;
-}
-
-// Helmholtz sweeps of the fields in `which` (1 = u, 2 = v, 3 = both): U,V -> TMPU,TMPV, then
-// swap so NS_ARR_U/V stay "current".  Partials: u at part[0, nb), v at part[nb, 2 nb).
-int helm_sweep(ns_solver* s, double alpha, double* part, int which = 3) {
-    const int nb = nsg::launch_helm_sweep(s->k, s->g, s->c, alpha, s->omega_v, s->arr[NS_ARR_U], s->arr[NS_ARR_V],
-                                          s->arr[NS_ARR_TMPU], s->arr[NS_ARR_TMPV], s->arr[NS_ARR_RU],
-                                          s->arr[NS_ARR_RV], part, s->st, which);
-    if (which & 1) std::swap(s->arr[NS_ARR_U], s->arr[NS_ARR_TMPU]);
-    if (which & 2) std::swap(s->arr[NS_ARR_V], s->arr[NS_ARR_TMPV]);
-    return nb;
-}
-
-// three Helmholtz sweeps in one pass (k_sweep3; with `part`: + the output residual, one rank), then
-// swap; a residual pass of one component is HIP-event timed like the pairs (24 B/cell either way:
-// the bench's Helmholtz-pass roofline)
-int helm_sweep3(ns_solver* s, double alpha, int which, double* part = nullptr) {
-    const bool t = s->timing && which != 3 && part;
-    if (t) {
-        if (s->hev.size() < 2 * (size_t)(s->hn + 1)) {
-            const size_t old = s->hev.size();
-            s->hev.resize(2 * (size_t)(s->hn + 8));
-            for (size_t k = old; k < s->hev.size(); k++)
-                if (hipEventCreate(&s->hev[k]) != hipSuccess) { set_err("hipEventCreate failed"); return -1; }
-        }
-        if (t_begin(s, s->hev[2 * s->hn], s->hev[2 * s->hn + 1]) != 0) return -1;
-    }
-    const int nb = nsg::launch_helm_sweep3(s->k, s->g, s->c, alpha, s->omega_v, s->arr[NS_ARR_U], s->arr[NS_ARR_V],
-                                           s->arr[NS_ARR_TMPU], s->arr[NS_ARR_TMPV], s->arr[NS_ARR_RU],
-                                           s->arr[NS_ARR_RV], s->st, which, part);
-    if (nb < 0) return nb;
-    if (t) {
-        if (t_end(s, s->hev[2 * s->hn], s->hev[2 * s->hn + 1]) != 0) return -1;
-        if (s->hcomp.size() <= (size_t)s->hn) s->hcomp.resize(s->hn + 8, 1);
-        s->hcomp[s->hn++] = 1;
-    }
-    if (which & 1) std::swap(s->arr[NS_ARR_U], s->arr[NS_ARR_TMPU]);
-    if (which & 2) std::swap(s->arr[NS_ARR_V], s->arr[NS_ARR_TMPV]);
-    return nb;
-}
-
-// two Helmholtz sweeps in one pass (temporal blocking), then swap
-int helm_sweep2(ns_solver* s, double alpha, double* part, int which = 3) {
-    // timing: one-component passes only (the bench's 24 B/cell roofline figure)
-    const bool t = s->timing && which != 3;
-    if (t) {
-        if (s->hev.size() < 2 * (size_t)(s->hn + 1)) {
-            const size_t old = s->hev.size();
-            s->hev.resize(2 * (size_t)(s->hn + 8));
-            for (size_t k = old; k < s->hev.size(); k++)
-                if (hipEventCreate(&s->hev[k]) != hipSuccess) { set_err("hipEventCreate failed"); return -1; }
-        }
-        if (t_begin(s, s->hev[2 * s->hn], s->hev[2 * s->hn + 1]) != 0) return -1;
-    }
-    const int nb = nsg::launch_helm_sweep2(s->k, s->g, s->c, alpha, s->omega_v, s->arr[NS_ARR_U], s->arr[NS_ARR_V],
-                                           s->arr[NS_ARR_TMPU], s->arr[NS_ARR_TMPV], s->arr[NS_ARR_RU],
-                                           s->arr[NS_ARR_RV], part, s->st, which);
-    if (t) {
-        if (t_end(s, s->hev[2 * s->hn], s->hev[2 * s->hn + 1]) != 0) return -1;
-        if (s->hcomp.size() <= (size_t)s->hn) s->hcomp.resize(s->hn + 8, 1);
-        s->hcomp[s->hn++] = 1;
-    }
+// one Helmholtz pass of w (1, 2 or 3) sweeps of the fields in `which` (1 = u, 2 = v, 3 = both): U,V -> TMPU,TMPV,
+// then swap so NS_ARR_U/V stay "current".  Partials: u at part[0, nb), v at part[nb, 2 nb) (w = 3 with `part`: +
+// the output residual, one rank).  Timed: the one-component passes of two or three sweeps, the latter with its
+// residual stage only (24 B/cell either way: the bench's Helmholtz-pass roofline)
+int helm_pass(ns_solver* s, double alpha, int w, int which, double* part) {
+    Timing::Scope iv;
+    TCHK(s->tm.open(iv, nsg::T_HELM, s->timing && which != 3 && w >= 2 && (w == 2 || part)));
+    double *U = s->arr[NS_ARR_U], *V = s->arr[NS_ARR_V], *TU = s->arr[NS_ARR_TMPU], *TV = s->arr[NS_ARR_TMPV];
+    double *RU = s->arr[NS_ARR_RU], *RV = s->arr[NS_ARR_RV];
+    const int nb = w == 3 ? nsg::launch_helm_sweep3(s->k, s->g, s->c, alpha, s->omega_v, U, V, TU, TV, RU, RV, s->st, which, part)
+                 : w == 2 ? nsg::launch_helm_sweep2(s->k, s->g, s->c, alpha, s->omega_v, U, V, TU, TV, RU, RV, part, s->st, which)
+                          : nsg::launch_helm_sweep(s->k, s->g, s->c, alpha, s->omega_v, U, V, TU, TV, RU, RV, part, s->st, which);
+    if (w == 3 && nb < 0) return nb;
+    TCHK(iv.close());
     if (which & 1) std::swap(s->arr[NS_ARR_U], s->arr[NS_ARR_TMPU]);
     if (which & 2) std::swap(s->arr[NS_ARR_V], s->arr[NS_ARR_TMPV]);
     return nb;
@@ -752,17 +664,9 @@ int helm_sweeps(ns_solver* s, double alpha, int n, double* part_first, double* p
                                       {&s->g, s->arr[NS_ARR_RU], 6}, {&s->g, s->arr[NS_ARR_RV], 6}};
                 const int nr = s->helm_b_pend ? 4 : 2;
                 s->helm_b_pend = 0;
-                // (one rank: the two-field residual pass is HIP-event timed as two component passes)
-                const bool t2 = s->nranks == 1 && s->timing && part && w == 3;
-                if (t2) {
-                    if (s->hev.size() < 2 * (size_t)(s->hn + 1)) {
-                        const size_t old = s->hev.size();
-                        s->hev.resize(2 * (size_t)(s->hn + 8));
-                        for (size_t q = old; q < s->hev.size(); q++)
-                            if (hipEventCreate(&s->hev[q]) != hipSuccess) { set_err("hipEventCreate failed"); return -1; }
-                    }
-                    CHK(t_begin(s, s->hev[2 * s->hn], s->hev[2 * s->hn + 1]));
-                }
+                // (one rank: the two-field residual pass is timed as two component passes -- weight 2)
+                Timing::Scope iv;
+                TCHK(s->tm.open(iv, nsg::T_HELM, s->nranks == 1 && s->timing && part && w == 3, 2));
                 // (r5, deep ghost rows: the wall bands left u, v valid deep enough -- no exchange; the residual
                 // 3-sweep pass then also computes one row of each neighbour's slab, so that K3 finds u*, v*'s ghost
                 // row valid and needs no exchange either -- its residual summed over the slab's own rows)
@@ -790,11 +694,7 @@ int helm_sweeps(ns_solver* s, double alpha, int n, double* part_first, double* p
                 nb = valid ? pass() : overlapped(s, r, nr, pass);
                 s->u_ext = ex;
                 if (nb < 0) return nb;
-                if (t2) {
-                    CHK(t_end(s, s->hev[2 * s->hn], s->hev[2 * s->hn + 1]));
-                    if (s->hcomp.size() <= (size_t)s->hn) s->hcomp.resize(s->hn + 8, 1);
-                    s->hcomp[s->hn++] = 2;
-                }
+                TCHK(iv.close());
                 std::swap(s->arr[NS_ARR_U], s->arr[NS_ARR_TMPU]);
                 std::swap(s->arr[NS_ARR_V], s->arr[NS_ARR_TMPV]);
             } else {
@@ -804,8 +704,7 @@ int helm_sweeps(ns_solver* s, double alpha, int n, double* part_first, double* p
                 }
                 if (which == 3) CHK(halo(s, {s->arr[NS_ARR_U], s->arr[NS_ARR_V]}, hw));
                 else if (w <= 2) CHK(halo(s, {s->arr[which == 1 ? NS_ARR_U : NS_ARR_V]}, hw));
-                nb = w == 3 ? helm_sweep3(s, alpha, which, part)
-                            : (w >= 2 ? helm_sweep2(s, alpha, part, which) : helm_sweep(s, alpha, part, which));
+                nb = helm_pass(s, alpha, w, which, part);
                 if (nb < 0) return NS_EHIP;
             }
             const int at = w >= 2 ? k + w : k;   // a multi-sweep pass reports its output's residual
@@ -950,24 +849,21 @@ int helm_band(ns_solver* s, double alpha) {
         return 0;
     }
     const bool tb = s->timing && s->in_step && s->nranks == 1;   // (r6: the bench's band line)
-    if (tb) CHK(ensure_kev(s));
     if (s->k.band6 && s->nranks == 1 && rounds == 2) {
         // (r6) one rank, 6 sweeps: ONE launch of 64 x 64 tiles with their 12-cell cone (k_helm_band6) into the
         // scratch planes, then the band cells' copy-back -- 80 B per band cell instead of 2 x 48 (one timed
         // interval: the bench's band line is the pair)
-        if (tb) CHK(t_begin(s, s->kev[8], s->kev[9]));
+        Timing::Scope iv;
+        TCHK(s->tm.open(iv, nsg::T_BAND, tb));
         const int n = nsg::launch_helm_band(s->g, s->c, alpha, s->omega_v, U, V, U, V, TU, TV, s->arr[NS_ARR_RU],
                                             s->arr[NS_ARR_RV], s->band_w, 2, s->st);
         if (n >= 0) {
             nsg::launch_helm_band(s->g, s->c, alpha, s->omega_v, U, V, TU, TV, U, V, s->arr[NS_ARR_RU],
                                   s->arr[NS_ARR_RV], s->band_w, 3, s->st);
-            if (tb) {
-                CHK(t_end(s, s->kev[8], s->kev[9]));
-                s->band_timed = 1;
-            }
+            TCHK(iv.close());
             return 0;
         }
-        if (tb) CHK(t_end(s, s->kev[8], s->kev[9]));   // (unsupported here: the launches of 3 below)
+        // (unsupported here: the interval is dropped with its scope; the launches of 3 below)
     }
     for (int k = 0; k < rounds; k++) {
         const bool odd = k & 1;
@@ -977,10 +873,10 @@ int helm_band(ns_solver* s, double alpha) {
                                          s->band_w, 0, s->st);
         };
         if (tb && k < 2) {
-            CHK(t_begin(s, s->kev[8 + 2 * k], s->kev[9 + 2 * k]));
+            Timing::Scope iv;
+            TCHK(s->tm.open(iv, nsg::T_BAND));
             launch();
-            CHK(t_end(s, s->kev[8 + 2 * k], s->kev[9 + 2 * k]));
-            s->band_timed = k + 1;
+            TCHK(iv.close());
         } else if (s->nranks > 1) {
             // the exchange overlapped with the tiles that read no neighbour's rows
             const HaloReq r[4] = {{&s->g, odd ? TU : U, 6}, {&s->g, odd ? TV : V, 6},
@@ -1220,32 +1116,24 @@ int pois_solve(ns_solver* s, int* its, double* res, ns_stats* stt) {
     const double tol2 = s->rtol * s->rtol;
     int sweeps = 0, batch = s->pois_batch0, prev_at = -1;
     double prev_r2 = -1;
-    double tms = 0.0;
-    int tn = 0, nchk = 0;
+    int nchk = 0;
     for (;;) {
         const int n = std::min(batch, s->max_iters - sweeps);
-        if (s->timing) CHK(ensure_events(s, 2 * (size_t)n));
         int nb = 0;
         for (int k = 0; k < n; k++) {
             double* part = k == n - 1 ? s->part : nullptr;
             CHK(halo(s, {s->arr[NS_ARR_PHI]}, 2));
-            if (s->timing) CHK(t_begin(s, s->ev[2 * k], s->ev[2 * k + 1]));
+            Timing::Scope iv;
+            TCHK(s->tm.open(iv, nsg::T_SWEEP, s->timing));
             nb = pois_sweep(s, part);
-            if (s->timing) CHK(t_end(s, s->ev[2 * k], s->ev[2 * k + 1]));
+            TCHK(iv.close());
         }
         sweeps += n;
         nsg::launch_reduce_sum(s->part, nb, 1, s->scal + S_RES, s->st);
         CHK(allreduce(s, s->scal + S_RES, 1, ncclSum));
         CHK(fetch(s));
         nchk++;
-        if (s->timing) {
-            for (int k = 0; k < n; k++) {
-                float ms = 0.f;
-                HIPCHK(hipEventElapsedTime(&ms, s->ev[2 * k], s->ev[2 * k + 1]));
-                tms += ms;
-            }
-            tn += n;
-        }
+        TCHK(s->tm.drain(nsg::T_MG, stt));
         const double r2 = s->hs[S_RES], b2 = s->hs[S_SHIFT + 1];
         *res = b2 > 0 ? std::sqrt(r2 / b2) : std::sqrt(r2);
         if (!std::isfinite(r2)) { set_err("Poisson residual is not finite"); *its = sweeps; return NS_EDIVERGE; }
@@ -1257,11 +1145,7 @@ int pois_solve(ns_solver* s, int* its, double* res, ns_stats* stt) {
         batch = nbatch;
     }
     *its = sweeps;
-    if (stt) {
-        stt->t_poisson_kernel_ms += tms;
-        stt->n_poisson_kernels += tn;
-        stt->n_checks += nchk;
-    }
+    if (stt) stt->n_checks += nchk;
     return 0;
 }
 
@@ -1431,19 +1315,19 @@ int zero_phi(ns_solver* s, int l) {
 // fused restriction pass when it is the level's first pre-smoothing pass, or the LDS coarse solve
 bool zero_ok(const ns_solver* s, int l);
 
-int mg_smooth(ns_solver* s, int l, int n, int* tn, int ev0) {
+int mg_smooth(ns_solver* s, int l, int n) {
     MgLevel& L = level(s, l);
     if (n > 0) CHK(flush_b(s, l));
     if (n > 0) CHK(zero_phi(s, l));
     for (int k = 0; k < n;) {
         const int w = (n - k >= 2 && pair_level(s, l)) ? 2 : 1;   // two sweeps per HBM pass
         CHK(halo_l(s, l, {L.phi}, 2 * w));
-        const bool t = s->timing && l == 0 && (!s->pc_active || s->pc_timing);
-        if (t) { CHK(t_begin(s, s->ev[2 * (ev0 + *tn)], s->ev[2 * (ev0 + *tn) + 1])); s->evtag[ev0 + *tn] = 0; }
+        Timing::Scope iv;
+        TCHK(s->tm.open(iv, nsg::T_SWEEP, s->timing && l == 0));
         const double* sh = l == 0 ? shift0(s) : nullptr;
         if (w == 2) nsg::launch_pois_rbsor2(s->k, L.g, L.c, s->mg_omega_s, L.phi, L.tmp, L.b, sh, nullptr, s->st);
         else nsg::launch_pois_rbsor(s->k, L.g, L.c, s->mg_omega_s, L.phi, L.tmp, L.b, sh, nullptr, s->st);
-        if (t) { CHK(t_end(s, s->ev[2 * (ev0 + *tn)], s->ev[2 * (ev0 + *tn) + 1])); (*tn)++; }
+        TCHK(iv.close());
         std::swap(L.phi, L.tmp);
         if (l == 0) { s->arr[NS_ARR_PHI] = L.phi; s->arr[NS_ARR_TMP] = L.tmp; }
         k += w;
@@ -1496,7 +1380,7 @@ int mg_coarse(ns_solver* s) {
 // one restriction pass it then discarded; two more RB sweeps shrink a cycle's output residual
 // only ~1.2x -- the post-smoothed residual is smooth -- so the counts stay the same.)
 template <class Check>
-int mg_vcycle(ns_solver* s, int* tn, int ev0, Check&& check, bool want_check, bool* done) {
+int mg_vcycle(ns_solver* s, Check&& check, bool want_check, bool* done) {
     const int nl = (int)s->lv.size();
     *done = false;
     for (int l = 0; l < nl - 1; l++) {
@@ -1508,37 +1392,35 @@ int mg_vcycle(ns_solver* s, int* tn, int ev0, Check&& check, bool want_check, bo
         // the coarse level's first pass takes its iterate as zero: the restriction stores no zeros
         const bool czero = zero_ok(s, l + 1);
         double* pcz = czero ? nullptr : cv.phi;
+        Timing::Scope iv;   // (the level-0 passes are timed; a preconditioner's only when the solve asks: tm.mute)
         if (l == 0 && s->gin_pending) {
             // the solve's first restriction pass with its input, the phi extrapolation, formed per
             // row from the history planes (k_sweep2_gin); it writes PHI (extrapolate_phi left the
             // output plane there and TMP free), so no swap
             s->gin_pending = false;
-            const bool t = s->timing && (!s->pc_active || s->pc_timing);
-            if (t) { CHK(t_begin(s, s->ev[2 * (ev0 + *tn)], s->ev[2 * (ev0 + *tn) + 1])); s->evtag[ev0 + *tn] = 3; }
+            TCHK(s->tm.open(iv, nsg::T_GUESS, s->timing));
             nb = nsg::launch_pois_rbsor2_restrict_guess(s->k, F.g, F.c, s->mg_omega_s, s->gin_src[0], F.phi, F.b, sh, cv.g,
                                                         cv.b, pcz, s->part, s->gin_src[1], s->gin_src[2],
                                                         s->gin_src[3], s->gin_c, s->st);
             if (nb < 0) { set_err("guess restriction pass does not fit"); return NS_EINVAL; }
-            if (t) { CHK(t_end(s, s->ev[2 * (ev0 + *tn)], s->ev[2 * (ev0 + *tn) + 1])); (*tn)++; }
+            TCHK(iv.close());
         } else if (l == 0 && s->p_pending) {
             // the previous cycle's prolongation pass (deferred: its output was not checked) and this
             // cycle's restriction pass in one (k_sweep4); level 1's phi still holds that correction
             s->p_pending = false;
-            const bool t = s->timing && (!s->pc_active || s->pc_timing);
-            if (t) { CHK(t_begin(s, s->ev[2 * (ev0 + *tn)], s->ev[2 * (ev0 + *tn) + 1])); s->evtag[ev0 + *tn] = 2; }
+            TCHK(s->tm.open(iv, nsg::T_CYCLE, s->timing));
             nb = nsg::launch_pois_sweep4(s->k, F.g, F.c, s->mg_omega_s, F.phi, F.tmp, F.b, sh, cv.g, cv.phi, cv.b, nullptr,
                                          s->part, s->st);
             if (nb < 0) { set_err("V-cycle boundary pass does not fit"); return NS_EINVAL; }
-            if (t) { CHK(t_end(s, s->ev[2 * (ev0 + *tn)], s->ev[2 * (ev0 + *tn) + 1])); (*tn)++; }
+            TCHK(iv.close());
             std::swap(F.phi, F.tmp);
             s->arr[NS_ARR_PHI] = F.phi; s->arr[NS_ARR_TMP] = F.tmp;
         } else if (fused_restrict(s, l)) {
             // last two pre-smoothing sweeps + residual + restriction in one HBM pass
-            CHK(mg_smooth(s, l, s->mg_pre - 2, tn, ev0));
+            CHK(mg_smooth(s, l, s->mg_pre - 2));
             const bool zin = F.zero;   // (then the pass reads neither phi nor its ghost rows)
             F.zero = false;
-            const bool t = s->timing && l == 0 && (!s->pc_active || s->pc_timing);
-            if (t) { CHK(t_begin(s, s->ev[2 * (ev0 + *tn)], s->ev[2 * (ev0 + *tn) + 1])); s->evtag[ev0 + *tn] = 1; }
+            TCHK(s->tm.open(iv, nsg::T_RESTRICT, s->timing && l == 0));
             if (tile_level(s, l)) {
                 CHK(flush_b(s, l));
                 if (!zin) CHK(halo_l(s, l, {F.phi}, 5));
@@ -1567,12 +1449,12 @@ int mg_vcycle(ns_solver* s, int* tn, int ev0, Check&& check, bool want_check, bo
                     F.phi_ghost = true;
                 }
             }
-            if (t) { CHK(t_end(s, s->ev[2 * (ev0 + *tn)], s->ev[2 * (ev0 + *tn) + 1])); (*tn)++; }
+            TCHK(iv.close());
             std::swap(F.phi, F.tmp);
             if (l == 0) { s->arr[NS_ARR_PHI] = F.phi; s->arr[NS_ARR_TMP] = F.tmp; }
         } else {
             CHK(zero_phi(s, l));
-            CHK(mg_smooth(s, l, s->mg_pre, tn, ev0));
+            CHK(mg_smooth(s, l, s->mg_pre));
             CHK(flush_b(s, l));
             CHK(halo_l(s, l, {F.phi}, 1));
             nb = nsg::launch_restrict(F.g, F.c, F.phi, F.b, sh, cv.g, C.c, cv.b, cv.phi, s->part, s->st);
@@ -1599,7 +1481,6 @@ int mg_vcycle(ns_solver* s, int* tn, int ev0, Check&& check, bool want_check, bo
         } else if (fused_prolong(s, l)) {
             // prolongation + the first two post-smoothing sweeps in one HBM pass; the coarse
             // and fine ghost rows travel in one group
-            const bool t = s->timing && l == 0 && (!s->pc_active || s->pc_timing);
             const double* shp = l == 0 ? shift0(s) : nullptr;
             // the finest level's last pass also sums its output residual (the convergence check)
             double* pp = (l == 0 && want_check && s->mg_post == 2) ? s->part : nullptr;
@@ -1609,7 +1490,8 @@ int mg_vcycle(ns_solver* s, int* tn, int ev0, Check&& check, bool want_check, bo
                     : nsg::launch_pois_rbsor2_prolong(s->k, F.g, F.c, s->mg_omega_s, F.phi, F.tmp, F.b, shp, cv.g, cv.phi,
                                                       pp, s->st);
             };
-            if (t) { CHK(t_begin(s, s->ev[2 * (ev0 + *tn)], s->ev[2 * (ev0 + *tn) + 1])); s->evtag[ev0 + *tn] = 0; }
+            Timing::Scope iv;
+            TCHK(s->tm.open(iv, nsg::T_SWEEP, s->timing && l == 0));
             int n;
             if (F.repl) {
                 n = pass();
@@ -1630,14 +1512,14 @@ int mg_vcycle(ns_solver* s, int* tn, int ev0, Check&& check, bool want_check, bo
                 if (n < 0) return n;
             }
             if (pp) nb_out = n;
-            if (t) { CHK(t_end(s, s->ev[2 * (ev0 + *tn)], s->ev[2 * (ev0 + *tn) + 1])); (*tn)++; }
+            TCHK(iv.close());
             std::swap(F.phi, F.tmp);
             if (l == 0) { s->arr[NS_ARR_PHI] = F.phi; s->arr[NS_ARR_TMP] = F.tmp; }
-            CHK(mg_smooth(s, l, s->mg_post - 2, tn, ev0));
+            CHK(mg_smooth(s, l, s->mg_post - 2));
         } else {
             if (!cv.gather) CHK(halo_l(s, l + 1, {C.phi}, 1));
             nsg::launch_prolong(F.g, F.phi, cv.g, cv.phi, s->st);
-            CHK(mg_smooth(s, l, s->mg_post, tn, ev0));
+            CHK(mg_smooth(s, l, s->mg_post));
         }
     }
     if (want_check && nl > 1) {
@@ -1661,9 +1543,7 @@ int pois_solve_mg(ns_solver* s, int* its, double* res, ns_stats* stt) {
     s->p_pending = false;
     const double tol2 = s->rtol * s->rtol;
     const int maxc = std::min(s->max_iters, 1000);
-    int cyc = 0, tn = 0, nchk = 0;   // cyc: V-cycles done before the current one
-    double tms = 0.0;
-    const int per_cycle = s->mg_pre + s->mg_post;
+    int cyc = 0, nchk = 0;   // cyc: V-cycles done before the current one
     // residual checks (host syncs): after cycle 0, then where the contraction rate (measured
     // between this solve's checks, else the previous solve's) predicts convergence -- the
     // cycles in between run without a host round trip
@@ -1697,23 +1577,7 @@ int pois_solve_mg(ns_solver* s, int* its, double* res, ns_stats* stt) {
             CHK(fetch(s));
         }
         nchk++;
-        if (s->timing) {
-            for (int k = 0; k < tn; k++) {
-                float ms = 0.f;
-                HIPCHK(hipEventElapsedTime(&ms, s->ev[2 * k], s->ev[2 * k + 1]));
-                if (s->evtag[k] == 2) {
-                    if (stt) { stt->t_cycle_kernel_ms += ms; stt->n_cycle_kernels++; }
-                } else if (s->evtag[k] == 3) {
-                    if (stt) { stt->t_guess_kernel_ms += ms; stt->n_guess_kernels++; }
-                } else if (s->evtag[k]) {
-                    if (stt) { stt->t_restrict_kernel_ms += ms; stt->n_restrict_kernels++; }
-                } else {
-                    tms += ms;
-                    if (stt) stt->n_poisson_kernels++;
-                }
-            }
-            tn = 0;
-        }
+        TCHK(s->tm.drain(nsg::T_MG, stt));
         const double r2 = s->hs[S_RES], b2 = s->hs[S_SHIFT + 1];
         *res = b2 > 0 ? std::sqrt(r2 / b2) : std::sqrt(r2);
         if (s->k.verbose) fprintf(stderr, "nsgpu poisson: after %d V-cycles rel. residual %.3e\n", cycles, *res);
@@ -1744,11 +1608,10 @@ int pois_solve_mg(ns_solver* s, int* its, double* res, ns_stats* stt) {
         return 0;
     };
     for (;;) {
-        if (s->timing) CHK(ensure_events(s, 2 * (size_t)(tn + per_cycle + 2)));
         bool done = false;
         // (the output residual only on the cycles the check reads: the pass without it keeps 3
         // rows in flight, 97.5 vs 101 us at 4096^2)
-        CHK(mg_vcycle(s, &tn, 0, check, cyc + 1 >= next_chk || cyc + 1 >= maxc, &done));
+        CHK(mg_vcycle(s, check, cyc + 1 >= next_chk || cyc + 1 >= maxc, &done));
         cyc++;
         if (done) break;
     }
@@ -1765,10 +1628,7 @@ int pois_solve_mg(ns_solver* s, int* its, double* res, ns_stats* stt) {
     s->mg_hist[0] = need;
     s->last_cycles = s->cur_cycles = cycles;
     s->gin_pending = false;
-    if (stt) {
-        stt->t_poisson_kernel_ms += tms;
-        stt->n_checks += nchk;
-    }
+    if (stt) stt->n_checks += nchk;
     return 0;
 }
 
@@ -1786,7 +1646,7 @@ int pois_solve_mg(ns_solver* s, int* its, double* res, ns_stats* stt) {
 // z = M^-1 q: one V-cycle of the preconditioner's multigrid with level-0 rhs q (no mean
 // shift), from z = 0 (wall closure) or from the outflow line solve's extension (line closure).  Level 0 is re-pointed at (z, scratch, q) and restored afterwards; the cycle's
 // ping-pong may leave the result in either buffer, so z / scratch are swapped to match.
-int mg_precond(ns_solver* s, double* q, double*& z, double*& scratch, int* tn = nullptr) {
+int mg_precond(ns_solver* s, double* q, double*& z, double*& scratch, bool timed = false) {
     double* sv[3] = {s->arr[NS_ARR_PHI], s->arr[NS_ARR_TMP], s->arr[NS_ARR_RPHI]};
     if (s->out_side >= 0) {
         // the outflow side's data: its 1-D line solve (on the side's slab; summed over ranks so
@@ -1815,13 +1675,11 @@ int mg_precond(ns_solver* s, double* q, double*& z, double*& scratch, int* tn = 
     s->arr[NS_ARR_TMP] = scratch;
     s->arr[NS_ARR_RPHI] = q;
     s->pc_active = true;
-    s->pc_timing = tn != nullptr;
-    int tn0 = 0;
-    if (tn) CHK(ensure_events(s, 2 * ((size_t)*tn + 2 * (s->mg_pre + s->mg_post) + 4)));
+    s->tm.mute = !timed;   // (its level-0 passes are timed for the outflow Poisson solve only)
     bool done = false;
-    const int rc = mg_vcycle(s, tn ? tn : &tn0, 0, [](int) { return 0; }, false, &done);
+    const int rc = mg_vcycle(s, [](int) { return 0; }, false, &done);
     s->pc_active = false;
-    s->pc_timing = false;
+    s->tm.mute = false;
     // (level 0's own pointer: a single-level hierarchy relaxes it in mg_coarse, which does not
     // track the swaps in s->arr)
     if (s->lv[0].phi != z) std::swap(z, scratch);
@@ -2062,12 +1920,13 @@ int bicgstab(ns_solver* s, const KrylovSolve& ks, int* its, double* res) {
         const int nb = nsg::launch_apply(s->k, ks.op, s->g, s->c, ks.alpha, x, y, q, s->part, s->st, gate ? stop : nullptr);
         return reduce(nb, 2);
     };
-    // timed level-0 passes of the preconditioner (events 0 .. tn), read after each host sync
-    int tn = 0;
+    // timed level-0 passes of the preconditioner, drained after each host sync (the multigrid's kinds: neither the
+    // guess pass -- gin_ok needs a solve without Krylov planes -- nor the cycle-boundary pass -- fuse4_level0 is
+    // off while preconditioning -- occurs here, so the shared table attributes them as ever: sweep or restriction)
     const bool timed = s->timing && ks.stt && ks.mg;
     auto precond = [&](double* q, int k) -> int {   // K[k] = M^-1 q
         if (ks.mg && ks.op == 0 && s->fps_pc) return fps_precond(s, q, s->kv[k], s->kv[8]);
-        if (ks.mg) return mg_precond(s, q, s->kv[k], s->kv[8], timed ? &tn : nullptr);
+        if (ks.mg) return mg_precond(s, q, s->kv[k], s->kv[8], timed);
         nsg::launch_diag_pc(ks.op, s->g, s->c, ks.alpha, q, s->kv[k], s->st, stop);
         return 0;
     };
@@ -2174,13 +2033,7 @@ int bicgstab(ns_solver* s, const KrylovSolve& ks, int* its, double* res) {
             HIPCHK(hipMemcpyAsync(s->scal + S_KRY + 5, s->ksc + nsg::KS_ALPHA, 2 * sizeof(double), hipMemcpyDeviceToDevice, s->st));
         }
         CHK(fetch(s));
-        for (int k = 0; k < tn; k++) {
-            float ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&ms, s->ev[2 * k], s->ev[2 * k + 1]));
-            if (s->evtag[k]) { ks.stt->t_restrict_kernel_ms += ms; ks.stt->n_restrict_kernels++; }
-            else { ks.stt->t_poisson_kernel_ms += ms; ks.stt->n_poisson_kernels++; }
-        }
-        tn = 0;
+        if (timed) TCHK(s->tm.drain(nsg::T_MG, ks.stt));
         const bool stopped = s->hs[S_KRY] != 0.0, brk = s->hs[S_KRY + 1] != 0.0;
         const int it = (int)s->hs[S_KRY + 2];
         const double r2 = stopped ? s->hs[S_KRY + 3] : s->hs[S_KRY + 4], b2 = kb2;
@@ -2340,11 +2193,12 @@ DenseLib& dense_lib() {
 int pois_solve_fps(ns_solver* s, int* its, double* res, ns_stats* stt) {
     const nsg::Geo& g = s->g;
     double* F = s->arr[NS_ARR_TMP];
-    // timed steps: the transforms by their dispatch stamps (one rank), the recurrences (five launches,
-    // the allgathers on slabs) between marker events
+    // timed steps: the transforms by their dispatch stamps (one rank; the dense ones, library calls, between marker
+    // events), the recurrences (five launches, the allgathers on slabs) between marker events
     const bool t = s->timing && s->in_step;
+    Timing::Scope tdct, ttri, tidct;
     // (fps_pre: K3's fused launch left this step's coefficients of b in F -- the recurrences take the
-    // mean off mode 0 -- and timed itself into kev[2..3])
+    // mean off mode 0 -- and timed itself as this solve's forward transform)
     const bool pre = s->fps_pre && s->in_step;
     s->fps_pre = false;
     nsg::FpsArgs fa = s->fa;
@@ -2362,33 +2216,26 @@ int pois_solve_fps(ns_solver* s, int* its, double* res, ns_stats* stt) {
         fam.m0b = s->m0b;
         fam.m0s = s->scal + S_SHIFT;
     }
-    if (t) {
-        CHK(ensure_kev(s));
-        if (!pre && !s->fps_dense) CHK(t_begin(s, s->kev[2], s->kev[3]));
-    }
+    TCHK(s->tm.open(tdct, nsg::T_FPS_DCT, t && (s->fps_dense || !pre), 1, s->fps_dense));
     // (the outflow row pair: the last rank's last local pair -- r6, slabs)
     const int oe_pair = oe && g.i0 + g.nxl == g.nx ? g.nxl / 2 - 1 : -1;
     if (s->fps_dense) {
         // (r6) the dense forward transform: F^T = F (N x N) b^T, one GEMM over the slab's rows (rocBLAS, column-major:
         // the row-major plane is its transpose); the mean comes off mode 0 in the recurrences (sh0, scale sh0s)
-        if (t) HIPCHK(hipEventRecord(s->kev[2], s->st));
         const double one = 1.0, zero = 0.0;
         if (dense_lib().dgemm(s->rb, rocblas_operation_none, rocblas_operation_none, g.ny, g.nxl, g.ny, &one, s->dF, g.ny,
                           s->arr[NS_ARR_RPHI], g.ld, &zero, F, g.ld) != rocblas_status_success) {
             set_err("direct Poisson solve: the dense forward transform (rocblas_dgemm) failed");
             return NS_EHIP;
         }
-        if (t) HIPCHK(hipEventRecord(s->kev[3], s->st));
         fa.sh0 = fa1.sh0 = fam.sh0 = s->scal + S_SHIFT;
     } else if (!pre && nsg::launch_fps_dct(s->k, false, s->arr[NS_ARR_RPHI], oe ? nullptr : s->scal + S_SHIFT, F, g.nxl, g.ny,
                                            g.ld, s->fps_tw, s->fps_wk, s->st, oe_pair, s->fps_tw8) < 0) {
         set_err("direct Poisson solve: ny = %d is not a supported power of two", g.ny);
         return NS_EINVAL;
     }
-    if (t) {
-        if (!pre && !s->fps_dense) CHK(t_end(s, s->kev[2], s->kev[3]));
-        HIPCHK(hipEventRecord(s->kev[4], s->st));
-    }
+    TCHK(tdct.close());
+    TCHK(s->tm.open(ttri, nsg::T_FPS_TRI, t, 1, true));
     if (oe && s->nranks > 1) {
         // (r6) slabs: the outflow row lives on the last rank -- its mode-0 shift 2 f'_{n-1} comes to every rank by one
         // scalar all-reduce before the recurrences, which then read it instead of their own last row
@@ -2424,11 +2271,8 @@ int pois_solve_fps(ns_solver* s, int* its, double* res, ns_stats* stt) {
     const int glo = s->fps_passes != 3 && s->deep && s->in_step && g.i0 > 0 ? 1 : 0;
     const int ghi = s->fps_passes != 3 && s->deep && s->in_step && g.i0 + g.nxl < g.nx ? 1 : 0;
     s->phi_ext = s->fps_passes != 3 && s->deep && s->in_step ? 1 : 0;
-    if (t) {
-        HIPCHK(hipEventRecord(s->kev[5], s->st));
-        if (s->fps_dense) HIPCHK(hipEventRecord(s->kev[6], s->st));
-        else CHK(t_begin(s, s->kev[6], s->kev[7]));
-    }
+    TCHK(ttri.close());
+    TCHK(s->tm.open(tidct, nsg::T_FPS_IDCT, t, 1, s->fps_dense));
     if (s->fps_dense) {   // (r6) phi^T = G (N x N) x^T over the rows the solve wrote
         const double one = 1.0, zero = 0.0;
         if (dense_lib().dgemm(s->rb, rocblas_operation_none, rocblas_operation_none, g.ny, g.nxl + glo + ghi, g.ny, &one,
@@ -2441,17 +2285,11 @@ int pois_solve_fps(ns_solver* s, int* its, double* res, ns_stats* stt) {
         nsg::launch_fps_dct(s->k, true, F - (ptrdiff_t)glo * g.ld, nullptr, s->arr[NS_ARR_PHI] - (ptrdiff_t)glo * g.ld,
                             g.nxl + glo + ghi, g.ny, g.ld, s->fps_tw, s->fps_wk, s->st, -1, s->fps_tw8);
     }
-    if (t) {
-        if (s->fps_dense) HIPCHK(hipEventRecord(s->kev[7], s->st));
-        else CHK(t_end(s, s->kev[6], s->kev[7]));
-    }
-    auto take_times = [&]() -> int {
-        if (!t || !stt) return 0;
-        HIPCHK(hipEventSynchronize(s->kev[7]));
-        stt->t_fps_dct_ms += kev_ms(s, 2);
-        stt->t_fps_tri_ms += kev_ms(s, 4);
-        stt->t_fps_idct_ms += kev_ms(s, 6);
-        stt->n_fps_solves++;
+    TCHK(tidct.close());
+    auto take_times = [&]() -> int {   // (after the solve's own last event: an unchecked solve has no host sync)
+        if (!t) return 0;
+        TCHK(tidct.wait());
+        TCHK(s->tm.drain(nsg::T_FPS, stt));
         return 0;
     };
     *its = 1;
@@ -3436,11 +3274,10 @@ int div_mean(ns_solver* s, int nb) {
 // rhs_phi itself only for a checked solve.  Slabs: the interior row pairs while the u*, v* ghost rows
 // travel, then the two edge pairs (as overlapped() does for the strip kernels)
 int divergence_fps(ns_solver* s) {
-    const bool t = s->timing;
-    if (t) {
-        CHK(ensure_kev(s));
-        CHK(t_begin(s, s->kev[2], s->kev[3]));
-    }
+    // (timed as the direct solve's forward transform; a speculative K3 formed again replaces its figure)
+    Timing::Scope iv;
+    if (s->timing) (void)s->tm.drain(nsg::tbit(nsg::T_FPS_DCT), nullptr);
+    TCHK(s->tm.open(iv, nsg::T_FPS_DCT, s->timing));
     double* b = fps_checks_next(s) ? s->arr[NS_ARR_RPHI] : nullptr;
     auto launch = [&](int phase) {
         return nsg::launch_fps_div(s->k, s->g, s->c, s->dt, s->arr[NS_ARR_U], s->arr[NS_ARR_V], b, s->arr[NS_ARR_TMP],
@@ -3466,7 +3303,7 @@ int divergence_fps(ns_solver* s) {
         set_err("direct Poisson solve: ny = %d is not a supported power of two", s->g.ny);
         return NS_EINVAL;
     }
-    if (t) CHK(t_end(s, s->kev[2], s->kev[3]));
+    TCHK(iv.close());
     s->fps_pre = true;
     s->fps_pre_b = b != nullptr;
     s->mean_pend = s->fps_defer && s->fps_passes == 2;
@@ -3513,11 +3350,8 @@ int helm_bnorm(ns_solver* s) {
 // K1 with its ghost rows (u, v width 2: MUSCL; phi width 1: grad phi^{n-1} on walls) in one
 // exchange group, overlapped with the interior tiles
 int rhs(ns_solver* s, bool defer_norm = false) {
-    const bool t = s->timing && s->in_step;
-    if (t) {
-        CHK(ensure_kev(s));
-        CHK(t_begin(s, s->kev[0], s->kev[1]));
-    }
+    Timing::Scope iv;
+    TCHK(s->tm.open(iv, nsg::T_K1, s->timing && s->in_step));
     int nb;
     if (s->deep && s->in_step) {
         // (r5) deep ghost rows: u, v (e + 2 rows: MUSCL), phi (e + 1: the wall terms' grad phi^{n-1}) and, when
@@ -3554,8 +3388,7 @@ int rhs(ns_solver* s, bool defer_norm = false) {
         s->corr_pend = 0;
         s->corr_k1 = 1;
         s->cu_ext = 0;
-        if (nb < 0) return nb;
-        if (t) CHK(t_end(s, s->kev[0], s->kev[1]));
+        TCHK(iv.close());
         // (the min / max and ||RHS||^2 partials in one launch; one rank: no bus, no all-reduce)
         // (r7) the host alone reads their results, after the Helmholtz pass: that check's reduction launch takes
         // them along (helm_solve, launch_reduce_step) instead of a launch of their own on the chain behind K1'
@@ -3574,7 +3407,7 @@ int rhs(ns_solver* s, bool defer_norm = false) {
         s->cu_ext = 0;
     }
     if (nb < 0) return nb;
-    if (t) CHK(t_end(s, s->kev[0], s->kev[1]));
+    TCHK(iv.close());
     // (r5, the bus: the rank's norms wait in S_HBNL for the Helmholtz check's allgather)
     const bool ub = defer_norm && bus_on(s);
     nsg::launch_reduce_sum(s->part, nb, 2, s->scal + (ub ? S_HBNL : S_HBN), s->st);
@@ -3601,30 +3434,22 @@ int correct_launch(ns_solver* s, double* part2) {
     s->guess_ready = 0;
     // (r5, deep slabs: the direct solve wrote phi's ghost rows -- no exchange)
     const bool have = s->deep && s->phi_ext && s->in_step;
-    const bool t5 = s->timing && s->in_step && !guess;   // (r6: the bench's K5 line; read at the next host sync)
-    if (t5) {
-        CHK(ensure_kev(s));
-        CHK(t_begin(s, s->kev[12], s->kev[13]));
-    }
-    const int nb = have ? [&]() {
+    // (r6: the bench's K5 line, drained at the next host sync -- the next step's after ns_step_async; a speculative
+    // K5 whose check failed runs again: its figure is replaced)
+    const bool t5 = s->timing && s->in_step && !guess;
+    Timing::Scope iv;
+    if (t5) (void)s->tm.drain(nsg::tbit(nsg::T_K5), nullptr);
+    TCHK(s->tm.open(iv, nsg::T_K5, t5));
+    auto launch = [&]() {
         if (guess)
             return nsg::launch_correct_guess(s->k, s->g, s->c, s->dt, s->arr[NS_ARR_U], s->arr[NS_ARR_V], s->arr[NS_ARR_TMPU],
                                              s->arr[NS_ARR_TMPV], s->arr[NS_ARR_PHI], part2, p.h[0], p.h[1], p.h[2], p.c,
                                              s->arr[NS_ARR_TMP], s->st);
         return nsg::launch_correct(s->k, s->g, s->c, s->dt, s->arr[NS_ARR_U], s->arr[NS_ARR_V], s->arr[NS_ARR_TMPU],
                                    s->arr[NS_ARR_TMPV], s->arr[NS_ARR_PHI], part2, s->st);
-    }() : overlapped(s, r, 1, [&]() {
-        if (guess)
-            return nsg::launch_correct_guess(s->k, s->g, s->c, s->dt, s->arr[NS_ARR_U], s->arr[NS_ARR_V], s->arr[NS_ARR_TMPU],
-                                             s->arr[NS_ARR_TMPV], s->arr[NS_ARR_PHI], part2, p.h[0], p.h[1], p.h[2], p.c,
-                                             s->arr[NS_ARR_TMP], s->st);
-        return nsg::launch_correct(s->k, s->g, s->c, s->dt, s->arr[NS_ARR_U], s->arr[NS_ARR_V], s->arr[NS_ARR_TMPU],
-                                   s->arr[NS_ARR_TMPV], s->arr[NS_ARR_PHI], part2, s->st);
-    });
-    if (t5 && nb >= 0) {
-        CHK(t_end(s, s->kev[12], s->kev[13]));
-        s->k5_pend = 1;
-    }
+    };
+    const int nb = have ? launch() : overlapped(s, r, 1, launch);
+    if (nb >= 0) TCHK(iv.close());
     if (guess && nb >= 0) {
         s->guess_ready = 1;
         s->guess_branch = p.branch;
@@ -3665,12 +3490,8 @@ int materialize(ns_solver* s) {
 // the right-hand side from u^n, v^n, T^n, cT0 (k_rhs_t): cT0 <- cT in place, rT, ||rT||^2 -> its BN2 slot
 int scalar_rhs(ns_solver* s) {
     auto& q = s->sc;
-    q.timed = 0;
-    if (s->timing && s->in_step) {
-        for (auto& e : q.kev)
-            if (!e) HIPCHK(hipEventCreate(&e));
-        CHK(t_begin(s, q.kev[0], q.kev[1]));
-    }
+    Timing::Scope iv;
+    TCHK(s->tm.open(iv, nsg::T_SCALAR_RHS, s->timing && s->in_step));
     // buoyancy: the variant that also folds the force into K1's RU / RV and CU / CV (which then hold convective-minus-
     // force) and sums the rewritten planes' squares into the partial block's third quarter
     double* pf = q.part + 4 * (size_t)nsg::max_partials(s->g);
@@ -3679,10 +3500,7 @@ int scalar_rhs(ns_solver* s) {
     const int nb = nsg::launch_rhs_t(s->k, s->g, s->c, q.neu, q.c, s->dt, q.pe, s->arr[NS_ARR_U], s->arr[NS_ARR_V], q.T,
                                      q.C, q.R, q.part, s->st, fb ? &by : nullptr);
     if (nb < 0) { set_err("the scalar's right-hand side: launch refused"); return NS_EHIP; }
-    if (s->timing && s->in_step) {
-        CHK(t_end(s, q.kev[0], q.kev[1]));
-        q.timed = 1;
-    }
+    TCHK(iv.close());
     nsg::launch_reduce_sum(q.part, nb, 1, q.scal + ns_solver::Scalar::BN2, s->st);
     // the Helmholtz tolerance is relative to ||RHS||^2 (S_HBN): K1's norms of the forced components are stale -- for
     // a fluid at rest 0, which no residual is below -- so the rewritten planes' own norms replace them here, on the
@@ -3752,13 +3570,7 @@ int scalar_end(ns_solver* s) {
     CHK(scalar_wait(s));
     q.last.t_rhs_kernel_ms = 0.0;
     q.last.n_rhs_kernels = 0;
-    if (q.timed) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, q.kev[0], q.kev[1]) == hipSuccess) {
-            q.last.t_rhs_kernel_ms = ms;
-            q.last.n_rhs_kernels = 1;
-        }
-    }
+    TCHK(s->tm.drain(nsg::tbit(nsg::T_SCALAR_RHS), nullptr, &q.last));
     return 0;
 }
 
@@ -4295,6 +4107,8 @@ int create_streams(ns_solver* s) {
         s->compute_cus = cus - s->comm_cus;
     }
     if (!s->st && hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking) != hipSuccess) { set_err("stream create failed"); return NS_EHIP; }
+    s->tm.stream = s->st;
+    s->tm.stamped = s->nranks == 1 && s->k.ext_timing;   // (slabs' timed calls exchange or split their launches: markers)
     if (hipEventCreateWithFlags(&s->fev, hipEventDisableTiming) != hipSuccess) { set_err("event create failed"); return NS_EHIP; }
     if (comm_on(s) &&
         ((!s->cst && hipStreamCreateWithFlags(&s->cst, hipStreamNonBlocking) != hipSuccess) ||
@@ -4569,8 +4383,7 @@ static void scalar_free(ns_solver* s) {
     if (q.scal) (void)hipFree(q.scal);
     if (q.hs) (void)hipHostFree(q.hs);
     if (q.ev) (void)hipEventDestroy(q.ev);
-    for (auto e : q.kev)
-        if (e) (void)hipEventDestroy(e);
+    (void)s->tm.drain(nsg::tbit(nsg::T_SCALAR_RHS), nullptr);   // (its events stay with the recorder)
     q = ns_solver::Scalar{};
 }
 
@@ -4582,8 +4395,7 @@ void ns_destroy(ns_solver* s) {
     if (s->comm) (void)ncclCommDestroy(s->comm);
     if (s->mev) (void)hipEventDestroy(s->mev);
     if (s->mm_host) (void)hipHostFree(s->mm_host);
-    for (auto e : s->ev) (void)hipEventDestroy(e);
-    for (auto e : s->hev) (void)hipEventDestroy(e);
+    s->tm.destroy();
     for (size_t l = 0; l < s->lv.size(); l++) {
         if (l > 0 && s->lv[l].mem) (void)hipFree(s->lv[l].mem);
         if (s->lv[l].coef) (void)hipFree(s->lv[l].coef);
@@ -4597,8 +4409,6 @@ void ns_destroy(ns_solver* s) {
     if (s->dense_mem) (void)hipFree(s->dense_mem);
     if (s->rb) (void)dense_lib().destroy(s->rb);
     if (s->cap_mem) (void)hipFree(s->cap_mem);
-    for (auto e : s->kev)
-        if (e) (void)hipEventDestroy(e);
     if (s->f32_mem) (void)hipFree(s->f32_mem);
     if (s->fc_mem) (void)hipFree(s->fc_mem);
     if (s->mband_tiles) (void)hipFree(s->mband_tiles);
@@ -4645,6 +4455,8 @@ static int step_body(ns_solver* s, ns_stats& st) {
 }
 
 static int step_body_(ns_solver* s, ns_stats& st) {
+    // (intervals a standalone kernel call or a failed step left behind are dropped; K5's wait for their drain below)
+    (void)s->tm.drain(~nsg::tbit(nsg::T_K5), nullptr);
     CHK(rhs(s, true));                                             // ConstructRHS_V       (:546)
     // the passive scalar sees u^n, v^n as K1 does (which wrote them in the deferred-K5 path): its right-hand side
     // and first batch of sweeps here, their residual read after the velocities' Helmholtz check
@@ -4656,34 +4468,15 @@ static int step_body_(ns_solver* s, ns_stats& st) {
     if (s->deep) {   // (r5: K1 computed the rhs deep into the neighbours' rows)
     } else if (s->nranks > 1 && s->overlap && s->cst && !s->g.fc && !s->k.tiled) s->helm_b_pend = 1;
     else CHK(halo(s, {s->arr[NS_ARR_RU], s->arr[NS_ARR_RV]}, 6));
-    s->hn = 0;
     // the Poisson initial guess (phi extrapolation) waits to hide the Helmholtz check's host sync
     s->extrap_pending = s->phim ? 1 : 0;
     CHK(helm_solve(s, &st.it_u, &st.res_u, &st.res_v));            // KSPSolve(uSolver) x2 (:547-548)
     if (s->extrap_pending) { s->extrap_pending = 0; CHK(extrapolate_phi(s)); }
     if (s->sc.on) CHK(scalar_end(s));
     st.it_v = st.it_u;
-    for (int k = 0; k < s->hn; k++) {   // (helm_solve's last residual check synchronised the stream)
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, s->hev[2 * k], s->hev[2 * k + 1]));
-        st.t_helm_kernel_ms += ms;
-        st.n_helm_kernels += (size_t)k < s->hcomp.size() ? s->hcomp[k] : 1;   // (per component: 24 B/cell)
-    }
-    s->hn = 0;
-    if (s->timing && s->kev[0]) {   // (K1 ended before the Helmholtz checks' host syncs)
-        st.t_rhs_kernel_ms += kev_ms(s, 0);
-        st.n_rhs_kernels++;
-    }
-    for (int k = 0; k < s->band_timed; k++) {   // (r6: the wall bands, before the same syncs)
-        st.t_band_kernel_ms += kev_ms(s, 8 + 2 * k);
-        st.n_band_kernels++;
-    }
-    s->band_timed = 0;
-    if (s->k5_pend) {   // (r6: the previous step's K5, ended before this step's first host sync)
-        st.t_k5_kernel_ms += kev_ms(s, 12);
-        st.n_k5_kernels++;
-        s->k5_pend = 0;
-    }
+    // (helm_solve's last residual check synchronised the stream: behind the Helmholtz passes -- per component, 24
+    // B/cell --, K1, the wall bands and the previous step's K5)
+    TCHK(s->tm.drain(nsg::tbit(nsg::T_HELM) | nsg::tbit(nsg::T_K1) | nsg::tbit(nsg::T_BAND) | nsg::tbit(nsg::T_K5), &st));
     if (!s->k3_spec) CHK(divergence(s));                           // ConstructRHS_phi + mean (:549-550)
     s->k3_spec = 0;
     CHK(consistent_rhs(s));                                        // stretched grids only
@@ -4724,11 +4517,7 @@ int ns_step(ns_solver* s, ns_stats* out) {
         st.n_allreduces++;
     }
     CHK(fetch(s));                                                 // VecMin/VecMax        (:554-557)
-    if (s->k5_pend) {   // (r6: this step's K5 -- the fetch synchronised the stream behind it)
-        st.t_k5_kernel_ms += kev_ms(s, 12);
-        st.n_k5_kernels++;
-        s->k5_pend = 0;
-    }
+    TCHK(s->tm.drain(nsg::tbit(nsg::T_K5), &st));   // (r6: this step's K5 -- the fetch synchronised the stream behind it)
     st.umin = s->hs[S_MM];
     st.umax = -s->hs[S_MM + 1];
     st.vmin = s->hs[S_MM + 2];
@@ -4934,15 +4723,15 @@ int ns_kernel(ns_solver* s, int which, int iters, double* out) {
         int nb = 0;
         CHK(halo(s, {s->arr[NS_ARR_RU], s->arr[NS_ARR_RV]}, 6));
         const int three = (s->k.sweep3 && s->nranks == 1 && !s->k.tiled && iters >= 4) ? 3 : 0;
-        if (three) helm_sweep3(s, alpha, 1), helm_sweep3(s, alpha, 2);
+        if (three) helm_pass(s, alpha, 3, 1, nullptr), helm_pass(s, alpha, 3, 2, nullptr);
         const int pairs = iters - three > 0 ? (iters - three - 1) / 2 : 0;
         for (int k = 0; k < pairs; k++) {
             CHK(halo(s, {s->arr[NS_ARR_U], s->arr[NS_ARR_V]}, 4));
-            helm_sweep2(s, alpha, nullptr);
+            helm_pass(s, alpha, 2, 3, nullptr);
         }
         for (int k = three + 2 * pairs; k < iters; k++) {
             CHK(halo(s, {s->arr[NS_ARR_U], s->arr[NS_ARR_V]}, 2));
-            nb = helm_sweep(s, alpha, k == iters - 1 ? s->part : nullptr);
+            nb = helm_pass(s, alpha, 1, 3, k == iters - 1 ? s->part : nullptr);
         }
         if (iters > 0) {
             nsg::launch_reduce_sum_segs(s->part, nb, 2, s->scal + S_RES, s->st);
@@ -5268,7 +5057,7 @@ int ns_time_poisson(ns_solver* s, int warmup, int iters, double* out) {
     if (s->kv[0]) { set_err("ns_time_poisson times the rectangle's sweeps (no NEUMANN side, no mask)"); return NS_EINVAL; }
     HIPCHK(hipSetDevice(s->device));
     nsg::set_compute_cus(s->compute_cus);
-    CHK(ensure_events(s, 2 * (size_t)iters));
+    (void)s->tm.drain(nsg::tbit(nsg::T_RAW), nullptr);   // (a failed call's leftovers)
     // NSGPU_TIME_PAIRS=1: time the two-sweep (temporally blocked) pass instead of a single sweep
     const bool pairs = s->k.time_pairs && s->poisson != NS_POISSON_JACOBI;
     auto one = [&](double* part) -> int {
@@ -5285,19 +5074,14 @@ int ns_time_poisson(ns_solver* s, int warmup, int iters, double* out) {
     };
     for (int k = 0; k < warmup; k++) CHK(one(nullptr));
     for (int k = 0; k < iters; k++) {
-        CHK(t_begin(s, s->ev[2 * k], s->ev[2 * k + 1]));
+        Timing::Scope iv;
+        TCHK(s->tm.open(iv, nsg::T_RAW));
         CHK(one(k == iters - 1 ? s->part : nullptr));
-        CHK(t_end(s, s->ev[2 * k], s->ev[2 * k + 1]));
+        TCHK(iv.close());
     }
     HIPCHK(hipStreamSynchronize(s->st));
-    double tot = 0.0;
-    for (int k = 0; k < iters; k++) {
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, s->ev[2 * k], s->ev[2 * k + 1]));
-        tot += ms;
-    }
-    float span = 0.f;
-    HIPCHK(hipEventElapsedTime(&span, s->ev[0], s->ev[2 * iters - 1]));
+    double tot = 0.0, span = 0.0;
+    TCHK(s->tm.drain_raw(&tot, &span));
     if (out) { out[0] = tot / iters; out[1] = tot; out[2] = span; }
     return 0;
 }
@@ -5309,26 +5093,21 @@ int ns_time_poisson_fp32(ns_solver* s, int warmup, int iters, double* out) {
     if (s->kv[0]) { set_err("ns_time_poisson_fp32 times the rectangle's sweeps (no NEUMANN side, no mask)"); return NS_EINVAL; }
     HIPCHK(hipSetDevice(s->device));
     nsg::set_compute_cus(s->compute_cus);
-    CHK(ensure_events(s, 2 * (size_t)iters));
+    (void)s->tm.drain(nsg::tbit(nsg::T_RAW), nullptr);   // (a failed call's leftovers)
     CHK(to_f32(s));
     int nb = 0;
     for (int k = 0; k < warmup; k++) CHK(pois_sweep32(s, nullptr, &nb));
     for (int k = 0; k < iters; k++) {
-        CHK(t_begin(s, s->ev[2 * k], s->ev[2 * k + 1]));
+        Timing::Scope iv;
+        TCHK(s->tm.open(iv, nsg::T_RAW));
         CHK(pois_sweep32(s, nullptr, &nb));
-        CHK(t_end(s, s->ev[2 * k], s->ev[2 * k + 1]));
+        TCHK(iv.close());
     }
     nsg::launch_reduce_sum(s->part, nb, 1, s->scal + S_RES, s->st);
     CHK(allreduce(s, s->scal + S_RES, 1, ncclSum));
     CHK(fetch(s));
-    double tot = 0.0;
-    for (int k = 0; k < iters; k++) {
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, s->ev[2 * k], s->ev[2 * k + 1]));
-        tot += ms;
-    }
-    float span = 0.f;
-    HIPCHK(hipEventElapsedTime(&span, s->ev[0], s->ev[2 * iters - 1]));
+    double tot = 0.0, span = 0.0;
+    TCHK(s->tm.drain_raw(&tot, &span));
     if (out) { out[0] = tot / iters; out[1] = tot; out[2] = span; out[3] = s->hs[S_RES]; }
     return 0;
 }
