@@ -22,9 +22,11 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/nsgpu.h"
+#include "ns_fps_tables.h"
 #include "ns_internal.h"
 #include "ns_timing.h"
 
@@ -231,7 +233,6 @@ struct ns_solver {
     // tridiagonal eigensolver at create, the transforms as rocBLAS GEMMs (F: forward, G: inverse, N x N each)
     bool fps_dense = false;
     rocblas_handle rb = nullptr;
-    double *dense_mem = nullptr, *dF = nullptr, *dG = nullptr;
     double area = 0.0;           // sum of the domain's cell areas
     double inv_area = 0.0;       // sum of their reciprocals
     int32_t* fc_mem = nullptr;   // masked domain: topology plane (g.fc) and edge table (g.et)
@@ -306,27 +307,31 @@ struct ns_solver {
     nsg::CapArgs cap{};
     void* cap_mem = nullptr;
     nsg::FpsArgs fa{};
-    double* fps_mem = nullptr;
-    const double *fps_tw = nullptr, *fps_wk = nullptr;
-    const double* fps_tw8 = nullptr;   // (r5) ny = 16384: the 8192-point halves' twiddles
+    // what the direct solve reads on the device beside fa (fps_setup; mem: its arena's ONE block, fa's arrays included)
+    struct FpsDev {
+        double* mem = nullptr;
+        const double *tw = nullptr, *wk = nullptr, *tw8 = nullptr;   // (r5) tw8, ny = 16384: the 8192-point halves' twiddles
+        // multi-rank: this rank's aggregate of a recurrence (2 x ld), every rank's (nranks x 2 x ld, one
+        // allgather per direction and solve) and the carry-in folded from them (ld)
+        double *ragg = nullptr, *gath = nullptr;
+        size_t n = 0;              // (r5) the allgather's slot: 2 x ld aggregates + (sum b, sum b^2) + padding
+        // (r5) ONE allgather per solve (NSGPU_FPS_ONEGATHER=0: two, A/B): the slot also carries the rank's backward
+        // aggregate with a zero forward carry-in (2 more ld), which is affine in that carry-in (FpsRank::bq); og_b /
+        // og_x1: the host tables B_p (every rank, per mode) and X1_p
+        bool og = false;
+        const double *og_b = nullptr, *og_x1 = nullptr;
+        // the deferred mean's tables of mode 0 (below): every chunk's E / BXl, the groups', the ranks' of the constant 1
+        const double *m0e = nullptr, *m0b = nullptr, *m0g = nullptr, *m0a = nullptr;
+        double *dense_mem = nullptr, *dF = nullptr, *dG = nullptr;   // the dense transforms (fps_dense): F | G
+    } fpd;
     int fps_passes = 2;          // full passes of the tridiagonal recurrences (NSGPU_FPS_PASSES=3: t1 / t2 / t3)
     long fps_solves = 0;
-    // multi-rank: this rank's aggregate of a recurrence (2 x ld), every rank's (nranks x 2 x ld, one
-    // allgather per direction and solve) and the carry-in folded from them (ld)
-    double *fps_ragg = nullptr, *fps_gath = nullptr;
-    size_t fps_n = 0;            // (r5) the allgather's slot: 2 x ld aggregates + (sum b, sum b^2) + padding
-    // (r5) ONE allgather per solve (NSGPU_FPS_ONEGATHER=0: two, A/B): the slot also carries the rank's backward
-    // aggregate with a zero forward carry-in (2 more ld), which is affine in that carry-in (FpsRank::bq); og_b /
-    // og_x1: the host tables B_p (every rank, per mode) and X1_p
-    bool fps_og = false, fps_og_mean = false;
-    const double *og_b = nullptr, *og_x1 = nullptr;
+    bool fps_og_mean = false;
     // r5, multi-rank rectangles on the direct solve: the fused K3's sums are not all-reduced -- they ride
     // on the recurrences' forward allgather (at 2 ld of each rank's slot), and the mean comes off mode 0
-    // afterwards, as the linear response of its aggregates to the constant ny * mean (host tables m0: every
-    // local chunk's E / BXl and group's aggregate of the constant 1, every rank's; fps_setup).
+    // afterwards, as the linear response of its aggregates to the constant ny * mean (fpd.m0*).
     // NSGPU_FPS_DEFER=0: the all-reduce before the solve (A/B).  mean_pend: this step's sums wait there
     bool fps_defer = false, mean_pend = false;
-    const double *m0e = nullptr, *m0b = nullptr, *m0g = nullptr, *m0a = nullptr;
     double fps_res = -1.0;       // the last checked solve's relative residual
     int kpred[3] = {1, 1, 1};    // (r5) the last BiCGStab solve's iterations: Poisson, Helmholtz u, v (bicgstab's batch)
     // (r5) a masked domain's Helmholtz solve on one rank by red-black SOR (k.mask_rb; k.mask_mt: up to 4 sweeps per
@@ -1700,7 +1705,7 @@ int fps_scan(ns_solver* s, bool backward);
 int fps_precond(ns_solver* s, const double* q, double* z, double* scratch, const int32_t* omask = nullptr) {
     const nsg::Geo& g = s->g;
     // ((r5) a masked domain whose box has the E outflow: its row pair transformed eliminated, as the channel's)
-    if (nsg::launch_fps_dct(s->k, false, q, nullptr, scratch, g.nxl, g.ny, g.ld, s->fps_tw, s->fps_wk, s->st,
+    if (nsg::launch_fps_dct(s->k, false, q, nullptr, scratch, g.nxl, g.ny, g.ld, s->fpd.tw, s->fpd.wk, s->st,
                             s->fa.outE ? g.nxl / 2 - 1 : -1) < 0) {
         set_err("direct Poisson preconditioner: ny = %d is not a supported power of two", g.ny);
         return NS_EINVAL;
@@ -1711,13 +1716,13 @@ int fps_precond(ns_solver* s, const double* q, double* z, double* scratch, const
     CHK(fps_scan(s, true));
     nsg::launch_fps_t2b(s->fa, scratch, s->st);
     if (omask) {   // (r6: z's masked-domain cells only)
-        if (nsg::launch_fps_idct_masked(s->k, scratch, z, g.nxl, g.ny, g.ld, s->fps_tw, s->fps_wk, s->st, omask) < 0) {
+        if (nsg::launch_fps_idct_masked(s->k, scratch, z, g.nxl, g.ny, g.ld, s->fpd.tw, s->fpd.wk, s->st, omask) < 0) {
             set_err("direct Poisson preconditioner: no masked inverse transform for ny = %d", g.ny);
             return NS_EINVAL;
         }
         return 0;
     }
-    nsg::launch_fps_dct(s->k, true, scratch, nullptr, z, g.nxl, g.ny, g.ld, s->fps_tw, s->fps_wk, s->st);
+    nsg::launch_fps_dct(s->k, true, scratch, nullptr, z, g.nxl, g.ny, g.ld, s->fpd.tw, s->fpd.wk, s->st);
     return 0;
 }
 
@@ -2098,9 +2103,9 @@ int allgather(ns_solver* s, const double* mine, double* all, size_t n) {
     return 0;
 }
 
-// every rank's aggregate of one recurrence direction (fps_ragg: 2 x ld, then the deferred mean's sums) into
-// fps_gath (slot q = rank q, fps_n doubles each)
-int fps_allgather(ns_solver* s) { return allgather(s, s->fps_ragg, s->fps_gath, s->fps_n); }
+// every rank's aggregate of one recurrence direction (fpd.ragg: 2 x ld, then the deferred mean's sums) into
+// fpd.gath (slot q = rank q, fpd.n doubles each)
+int fps_allgather(ns_solver* s) { return allgather(s, s->fpd.ragg, s->fpd.gath, s->fpd.n); }
 
 // the group scan of one direction; multi-rank: this rank's aggregate first (its carries from zero,
 // rewritten below), the allgather, the carry-in from the ranks before / after, then the scan from it
@@ -2110,47 +2115,47 @@ int fps_scan(ns_solver* s, bool backward) {
         nsg::launch_fps_scan(s->fa, backward, nsg::FpsRank{}, nullptr, s->st);
         return 0;
     }
-    if (s->fps_og) {
+    if (s->fpd.og) {
         // (r5) ONE allgather per solve: forward, the rank-local passes first -- the forward scan (this rank's
         // (E, P)), k_fps_mid without the chunk stores, the backward scan (its (X0, R) with a zero carry-in) --
         // then the allgather and the real forward scan; backward, the real scan with FpsRank::bq's carry-in
-        nsg::FpsRank R{s->fps_gath, s->nranks, s->rank, (int)s->fps_n};
+        nsg::FpsRank R{s->fpd.gath, s->nranks, s->rank, (int)s->fpd.n};
         if (backward) {
-            R.bq = s->og_b;
+            R.bq = s->fpd.og_b;
             if (s->fps_og_mean) {   // (the mean was deferred in this solve's forward pass: the same correction)
-                R.a1 = s->m0a;
-                R.x1 = s->og_x1;
+                R.a1 = s->fpd.m0a;
+                R.x1 = s->fpd.og_x1;
                 R.ncells = s->ncells;
             }
             nsg::launch_fps_scan(s->fa, true, R, nullptr, s->st);
             return 0;
         }
         if (s->mean_pend) {
-            R.a1 = s->m0a;
+            R.a1 = s->fpd.m0a;
             R.ncells = s->ncells;
         }
         const size_t ld = s->g.ld;
-        nsg::launch_fps_scan(s->fa, false, nsg::FpsRank{}, s->fps_ragg, s->st);
+        nsg::launch_fps_scan(s->fa, false, nsg::FpsRank{}, s->fpd.ragg, s->st);
         nsg::FpsArgs fl = s->fa;
         fl.mid_local = 1;
         nsg::launch_fps_mid(fl, s->arr[NS_ARR_TMP], s->st);
-        nsg::launch_fps_scan(s->fa, true, nsg::FpsRank{}, s->fps_ragg + 2 * ld + 8, s->st);
+        nsg::launch_fps_scan(s->fa, true, nsg::FpsRank{}, s->fpd.ragg + 2 * ld + 8, s->st);
         CHK(fps_allgather(s));
         s->fps_og_mean = s->mean_pend;   // (the backward carry's mode-0 correction needs the same sums)
         if (s->mean_pend) {
-            R.ge1 = s->m0g;
+            R.ge1 = s->fpd.m0g;
             R.shift = s->scal + S_SHIFT;
         }
         nsg::launch_fps_scan(s->fa, false, R, nullptr, s->st);
         return 0;
     }
-    nsg::launch_fps_scan(s->fa, backward, nsg::FpsRank{}, s->fps_ragg, s->st);
+    nsg::launch_fps_scan(s->fa, backward, nsg::FpsRank{}, s->fpd.ragg, s->st);
     CHK(fps_allgather(s));
     // (the other ranks' carry-in is folded inside the scan; r4 had a k_fps_rank_carry launch per direction)
-    nsg::FpsRank R{s->fps_gath, s->nranks, s->rank, (int)s->fps_n};
+    nsg::FpsRank R{s->fpd.gath, s->nranks, s->rank, (int)s->fpd.n};
     if (!backward && s->mean_pend) {   // (r5) the deferred mean: its sums came with the aggregates
-        R.a1 = s->m0a;
-        R.ge1 = s->m0g;
+        R.a1 = s->fpd.m0a;
+        R.ge1 = s->fpd.m0g;
         R.ncells = s->ncells;
         R.shift = s->scal + S_SHIFT;
     }
@@ -2212,8 +2217,8 @@ int pois_solve_fps(ns_solver* s, int* its, double* res, ns_stats* stt) {
     nsg::FpsArgs fa1 = fa, fam = fa;
     if (dm) {
         fa1.sh0 = nullptr;
-        fam.m0e = s->m0e;
-        fam.m0b = s->m0b;
+        fam.m0e = s->fpd.m0e;
+        fam.m0b = s->fpd.m0b;
         fam.m0s = s->scal + S_SHIFT;
     }
     TCHK(s->tm.open(tdct, nsg::T_FPS_DCT, t && (s->fps_dense || !pre), 1, s->fps_dense));
@@ -2223,14 +2228,14 @@ int pois_solve_fps(ns_solver* s, int* its, double* res, ns_stats* stt) {
         // (r6) the dense forward transform: F^T = F (N x N) b^T, one GEMM over the slab's rows (rocBLAS, column-major:
         // the row-major plane is its transpose); the mean comes off mode 0 in the recurrences (sh0, scale sh0s)
         const double one = 1.0, zero = 0.0;
-        if (dense_lib().dgemm(s->rb, rocblas_operation_none, rocblas_operation_none, g.ny, g.nxl, g.ny, &one, s->dF, g.ny,
+        if (dense_lib().dgemm(s->rb, rocblas_operation_none, rocblas_operation_none, g.ny, g.nxl, g.ny, &one, s->fpd.dF, g.ny,
                           s->arr[NS_ARR_RPHI], g.ld, &zero, F, g.ld) != rocblas_status_success) {
             set_err("direct Poisson solve: the dense forward transform (rocblas_dgemm) failed");
             return NS_EHIP;
         }
         fa.sh0 = fa1.sh0 = fam.sh0 = s->scal + S_SHIFT;
     } else if (!pre && nsg::launch_fps_dct(s->k, false, s->arr[NS_ARR_RPHI], oe ? nullptr : s->scal + S_SHIFT, F, g.nxl, g.ny,
-                                           g.ld, s->fps_tw, s->fps_wk, s->st, oe_pair, s->fps_tw8) < 0) {
+                                           g.ld, s->fpd.tw, s->fpd.wk, s->st, oe_pair, s->fpd.tw8) < 0) {
         set_err("direct Poisson solve: ny = %d is not a supported power of two", g.ny);
         return NS_EINVAL;
     }
@@ -2276,14 +2281,14 @@ int pois_solve_fps(ns_solver* s, int* its, double* res, ns_stats* stt) {
     if (s->fps_dense) {   // (r6) phi^T = G (N x N) x^T over the rows the solve wrote
         const double one = 1.0, zero = 0.0;
         if (dense_lib().dgemm(s->rb, rocblas_operation_none, rocblas_operation_none, g.ny, g.nxl + glo + ghi, g.ny, &one,
-                          s->dG, g.ny, F - (ptrdiff_t)glo * g.ld, g.ld, &zero,
+                          s->fpd.dG, g.ny, F - (ptrdiff_t)glo * g.ld, g.ld, &zero,
                           s->arr[NS_ARR_PHI] - (ptrdiff_t)glo * g.ld, g.ld) != rocblas_status_success) {
             set_err("direct Poisson solve: the dense inverse transform (rocblas_dgemm) failed");
             return NS_EHIP;
         }
     } else {
         nsg::launch_fps_dct(s->k, true, F - (ptrdiff_t)glo * g.ld, nullptr, s->arr[NS_ARR_PHI] - (ptrdiff_t)glo * g.ld,
-                            g.nxl + glo + ghi, g.ny, g.ld, s->fps_tw, s->fps_wk, s->st, -1, s->fps_tw8);
+                            g.nxl + glo + ghi, g.ny, g.ld, s->fpd.tw, s->fpd.wk, s->st, -1, s->fpd.tw8);
     }
     TCHK(tidct.close());
     auto take_times = [&]() -> int {   // (after the solve's own last event: an unchecked solve has no host sync)
@@ -2392,427 +2397,163 @@ int pois_solve_any(ns_solver* s, int* its, double* res, ns_stats* stt) {
     return pois_solve(s, its, res, stt);
 }
 
-// host tables of the direct solve (ns_create): twiddles, the modes' eigenvalues and every chunk's
-// entry pivot.  The pivots p_i(k) of Thomas' recurrence (ns_fps.hip) depend on the operator only:
-// the host runs the recurrence over the global rows up to the slab's end and keeps 1 / p of the row
-// before each chunk of this slab (0 before global row 0, whose pw is 0)
+// a bump allocator over ONE device block: the same list of (pointer, count) pairs gives the block's size (place(nullptr))
+// and then the pointers (place(base)), so a size and its carve cannot disagree; a host table is listed with its data, which
+// upload() copies.  Every table starts on a 16-byte boundary (doubles are read in pairs); count 0 keeps a null pointer
+struct Arena {
+    struct Item { void** p; size_t bytes; const void* src; };
+    std::vector<Item> items;
+    template <class T>
+    void add(T*& p, size_t n, const void* src = nullptr) { items.push_back({(void**)&p, n * sizeof(T), src}); }
+    template <class T>
+    void add(T*& p, const std::vector<std::remove_const_t<T>>& v) { add(p, v.size(), v.data()); }
+    size_t place(char* base) const {
+        size_t off = 0;
+        for (const Item& it : items) {
+            if (base && it.bytes) *it.p = base + off;
+            off += (it.bytes + 15) / 16 * 16;
+        }
+        return off;
+    }
+    hipError_t upload() const {
+        hipError_t e = hipSuccess;
+        for (const Item& it : items)
+            if (it.src && it.bytes && e == hipSuccess) e = hipMemcpy(*it.p, it.src, it.bytes, hipMemcpyHostToDevice);
+        return e;
+    }
+};
+
+// (r6) the dense y transforms: Ly's eigen-decomposition (the Poisson operator along y, ConstructLHS FluidSolver.cpp:113-131:
+// zero-flux faces, 2 / (h (h + h_nb)) toward each neighbour): S = H^1/2 Ly H^-1/2 is symmetric tridiagonal (diagonal
+// -(ps + pn), off-diagonal sqrt(pn_j ps_j+1)); rocSOLVER's divide and conquer gives its eigenpairs, the transforms F = Q^T
+// H^1/2, G = H^-1/2 Q (mode 0 = the zero eigenvalue, its vector H^1/2 1 set exactly).  mu <- the eigenvalues; F | G stay
+int fps_dense_setup(ns_solver* s, const std::vector<double>& hy, std::vector<double>& mu) {
+    const int N = s->g.ny;
+    std::vector<double> h3(3 * (size_t)N, 0.0);   // the diagonal, the off-diagonal (N - 1), H^1/2: as one upload
+    double sumhy = 0.0, *dg = h3.data(), *of = dg + N, *shy = of + N;
+    for (int j = 0; j < N; j++) {
+        const double ps = j > 0 ? 2.0 / (hy[j] * (hy[j] + hy[j - 1])) : 0.0;
+        const double pn = j < N - 1 ? 2.0 / (hy[j] * (hy[j] + hy[j + 1])) : 0.0;
+        dg[j] = -(ps + pn);
+        if (j < N - 1) of[j] = std::sqrt(pn * (2.0 / (hy[j + 1] * (hy[j + 1] + hy[j]))));
+        shy[j] = std::sqrt(hy[j]);
+        sumhy += hy[j];
+    }
+    DenseLib& DL = dense_lib();
+    if (!DL.ok) { set_err("the dense y transforms need librocblas / librocsolver (dlopen failed)"); return NS_EINVAL; }
+    if (DL.create(&s->rb) != rocblas_status_success) { set_err("rocblas_create_handle failed"); return NS_EHIP; }
+    if (DL.set_stream(s->rb, s->st) != rocblas_status_success) { set_err("rocblas_set_stream failed"); return NS_EHIP; }
+    const size_t nn = (size_t)N * N;
+    ns_solver::FpsDev& d = s->fpd;
+    HIPCHK(hipMalloc(&d.dense_mem, 2 * nn * sizeof(double)));
+    d.dF = d.dense_mem; d.dG = d.dF + nn;
+    struct Tmp { double* p = nullptr; ~Tmp() { (void)hipFree(p); } } tmp;   // Q, D / lambda, E, H^1/2, info: this call's
+    HIPCHK(hipMalloc(&tmp.p, (nn + 3 * (size_t)N + 8) * sizeof(double)));
+    double *dC = tmp.p, *dD = dC + nn, *dE = dD + N, *dS = dE + N;
+    rocblas_int* dinfo = reinterpret_cast<rocblas_int*>(dS + N);
+    HIPCHK(hipMemcpy(dD, h3.data(), h3.size() * sizeof(double), hipMemcpyHostToDevice));   // (dD | dE | dS)
+    if (DL.dstedc(s->rb, rocblas_evect_tridiagonal, N, dD, dE, dC, N, dinfo) != rocblas_status_success) {
+        set_err("rocsolver_dstedc failed (ny = %d)", N);
+        return NS_EHIP;
+    }
+    rocblas_int info = 0;
+    std::vector<double> lam(N);
+    HIPCHK(hipMemcpyAsync(&info, dinfo, sizeof(info), hipMemcpyDeviceToHost, s->st));
+    HIPCHK(hipMemcpyAsync(lam.data(), dD, N * sizeof(double), hipMemcpyDeviceToHost, s->st));
+    HIPCHK(hipStreamSynchronize(s->st));
+    if (info != 0) { set_err("rocsolver_dstedc: info %d (ny = %d)", (int)info, N); return NS_EHIP; }
+    // mode k: the (N - 1 - k)-th smallest eigenvalue (ascending from rocSOLVER): mode 0 the zero one
+    for (int k = 0; k < N; k++) mu[k] = k == 0 ? 0.0 : lam[N - 1 - k];
+    nsg::launch_dense_mats(dC, dS, 1.0 / std::sqrt(sumhy), N, d.dF, d.dG, s->st);
+    HIPCHK(hipStreamSynchronize(s->st));
+    s->fa.sh0s = std::sqrt(sumhy);   // (mode 0 of the constant 1: sum_j hy_j / sqrt(sum hy))
+    return 0;
+}
+
+// (r8) the FIXED chunks' device check: P from a run of k_fps_t1b itself (its general body on every chunk, a zero plane
+// -- P is the operator's), collapsed with beta and BR to one row per block (fps_fixed_collapse); FpsArgs' cfix / clast /
+// fixv are set only if a block keeps FIXED chunks.  Returns their count in *nfix
+int fps_fixed_check(ns_solver* s, const nsg::FpsOp& o, nsg::FpsTables& T, int* d_cfix, double* d_fixv, long* nfix) {
+    nsg::FpsArgs& a = s->fa;
+    if (T.cfix.empty()) return 0;
+    const size_t npl = (size_t)o.nxl * o.ld, nP = (size_t)a.nch * o.ld;
+    double* zero = nullptr;
+    HIPCHK(hipMalloc(&zero, npl * sizeof(double)));
+    HIPCHK(hipMemsetAsync(zero, 0, npl * sizeof(double), s->st));
+    nsg::launch_fps_t1b(a, zero, s->st);
+    std::vector<double> hP(nP), fv;
+    HIPCHK(hipMemcpyAsync(hP.data(), a.ca + nP, nP * sizeof(double), hipMemcpyDeviceToHost, s->st));
+    HIPCHK(hipStreamSynchronize(s->st));
+    HIPCHK(hipFree(zero));
+    *nfix = nsg::fps_fixed_collapse(o, T, hP, fv);
+    if (*nfix > 0) {
+        HIPCHK(hipMemcpy(d_fixv, fv.data(), fv.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_cfix, T.cfix.data(), T.cfix.size() * sizeof(int), hipMemcpyHostToDevice));
+        a.cfix = d_cfix; a.clast = T.clast; a.fixv = d_fixv;
+    }
+    return 0;
+}
+
+// what the direct solve reads on the device (ns_create): the host tables (ns_fps_tables.h; the dense transforms bring
+// their own eigenvalues), one arena for them and the recurrences' work arrays, the uploads, the FIXED chunks' check
 int fps_setup(ns_solver* s, const std::vector<double>& hy, const double* pw, const double* pe) {
     const nsg::Geo& g = s->g;
-    const int N = g.ny, ld = g.ld;
+    const int ld = g.ld, P = s->nranks;
+    ns_solver::FpsDev& d = s->fpd;
     nsg::FpsArgs& a = s->fa;
-    a.nx = g.nx; a.i0 = g.i0; a.nxl = g.nxl; a.ny = N; a.ld = ld;
-    a.nch = (g.nxl + nsg::FPS_M - 1) / nsg::FPS_M;
-    a.ngrp = (a.nch + nsg::FPS_G - 1) / nsg::FPS_G;
+    d.og = P > 1 && P <= 64 && s->fps_passes != 3 && s->k.fps_onegather;
+    nsg::FpsOp o;
+    o.nx = g.nx; o.ny = g.ny; o.ld = ld; o.i0 = g.i0; o.nxl = g.nxl; o.M = nsg::FPS_M; o.G = nsg::FPS_G;
+    for (int32_t rq = 0, q0 = 0, q1 = g.nx; rq < std::max(P, 1); rq++) {
+        if (P > 1) CHK(ns_slab_range(g.nx, P, rq, &q0, &q1));
+        o.ranks.push_back({q0, q1});
+    }
+    o.pw = pw; o.pe = pe; o.hy0 = hy[0]; o.outE = a.outE;
+    o.pmode = !s->fps_xuni || s->fps_dense ? 0 : s->k.fps_ptab;   // (r6: stretched -- none)
+    o.t8 = nsg::fps_log2(g.ny) < 0;   // (r5) ny = 16384: the two-half transforms (any other such ny: built, not read)
+    a.nx = g.nx; a.i0 = g.i0; a.nxl = g.nxl; a.ny = g.ny; a.ld = ld;
+    a.nch = o.nch(); a.ngrp = o.ngrp();
     a.pin = 1;   // (every side of the rectangle is zero-flux for phi: Lx 1 = 0)
-    const int nchp = a.ngrp * nsg::FPS_G;   // (t1 / t2 / t3 address whole groups' chunks)
-    const size_t n_tab = 4 * (size_t)N + (size_t)N, n_rp0 = (size_t)nchp * ld, n_g = (size_t)a.ngrp * ld;
-    // multi-rank: the allgather's own slot and every rank's (fps_n each), and the deferred mean's mode-0
-    // tables (chunks' E and BXl, groups', ranks' aggregates of the constant 1)
-    s->fps_og = s->nranks > 1 && s->nranks <= 64 && s->fps_passes != 3 && s->k.fps_onegather;
-    s->fps_n = (s->fps_og ? 4 : 2) * (size_t)ld + 8;
-    const size_t n_og = s->fps_og ? (size_t)s->nranks * ld + s->nranks : 0;
-    const size_t n_mr = s->nranks > 1 ? (size_t)(1 + s->nranks) * s->fps_n + 2 * (size_t)nchp + a.ngrp + s->nranks + n_og
-                                      : 0;
-    const size_t n_bt = 2 * (size_t)nchp * ld;
-    const size_t total = n_tab + n_rp0 + n_bt + 6 * n_g + 5 * (size_t)nchp * ld + n_mr + 8;
-    std::vector<double> h(n_tab + n_rp0 + n_bt, 0.0);
-    const double pi = 3.14159265358979323846;
-    for (int m = 0; m < N; m++) {
-        const double t = 2.0 * pi * ((double)m / N);
-        h[2 * m] = std::cos(t);
-        h[2 * m + 1] = -std::sin(t);
-        const double u = pi * ((double)m / (2.0 * N));
-        h[2 * N + 2 * m] = std::cos(u);
-        h[2 * N + 2 * m + 1] = -std::sin(u);
-        const double sn = std::sin(u);
-        h[4 * N + m] = -4.0 / (hy[0] * hy[0]) * sn * sn;   // -(2/hy^2)(1 - cos(pi m / N))
-    }
-    if (s->fps_dense) {
-        // (r6) Ly's eigen-decomposition (the Poisson operator along y, ConstructLHS FluidSolver.cpp:113-131: zero-flux
-        // faces, 2 / (h (h + h_nb)) toward each neighbour): S = H^1/2 Ly H^-1/2 is symmetric tridiagonal (diagonal
-        // -(ps + pn), off-diagonal sqrt(pn_j ps_j+1)); rocSOLVER's divide and conquer gives its eigenpairs, the
-        // transforms F = Q^T H^1/2, G = H^-1/2 Q (mode 0 = the zero eigenvalue, its vector H^1/2 1 set exactly)
-        std::vector<double> dg(N), of(std::max(N - 1, 1), 0.0), shy(N);
-        double sumhy = 0.0;
-        for (int j = 0; j < N; j++) {
-            const double ps = j > 0 ? 2.0 / (hy[j] * (hy[j] + hy[j - 1])) : 0.0;
-            const double pn = j < N - 1 ? 2.0 / (hy[j] * (hy[j] + hy[j + 1])) : 0.0;
-            dg[j] = -(ps + pn);
-            if (j < N - 1) of[j] = std::sqrt(pn * (2.0 / (hy[j + 1] * (hy[j + 1] + hy[j]))));
-            shy[j] = std::sqrt(hy[j]);
-            sumhy += hy[j];
-        }
-        DenseLib& DL = dense_lib();
-        if (!DL.ok) { set_err("the dense y transforms need librocblas / librocsolver (dlopen failed)"); return NS_EINVAL; }
-        if (DL.create(&s->rb) != rocblas_status_success) { set_err("rocblas_create_handle failed"); return NS_EHIP; }
-        if (DL.set_stream(s->rb, s->st) != rocblas_status_success) { set_err("rocblas_set_stream failed"); return NS_EHIP; }
-        const size_t nn = (size_t)N * N;
-        HIPCHK(hipMalloc(&s->dense_mem, (3 * nn + 3 * (size_t)N + 8) * sizeof(double)));
-        s->dF = s->dense_mem;
-        s->dG = s->dF + nn;
-        double *dC = s->dG + nn, *dD = dC + nn, *dE = dD + N, *dS = dE + N;
-        rocblas_int* dinfo = reinterpret_cast<rocblas_int*>(dS + N);
-        HIPCHK(hipMemcpy(dD, dg.data(), N * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dE, of.data(), std::max(N - 1, 1) * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dS, shy.data(), N * sizeof(double), hipMemcpyHostToDevice));
-        if (DL.dstedc(s->rb, rocblas_evect_tridiagonal, N, dD, dE, dC, N, dinfo) != rocblas_status_success) {
-            set_err("rocsolver_dstedc failed (ny = %d)", N);
-            return NS_EHIP;
-        }
-        rocblas_int info = 0;
-        std::vector<double> lam(N);
-        HIPCHK(hipMemcpyAsync(&info, dinfo, sizeof(info), hipMemcpyDeviceToHost, s->st));
-        HIPCHK(hipMemcpyAsync(lam.data(), dD, N * sizeof(double), hipMemcpyDeviceToHost, s->st));
-        HIPCHK(hipStreamSynchronize(s->st));
-        if (info != 0) { set_err("rocsolver_dstedc: info %d (ny = %d)", (int)info, N); return NS_EHIP; }
-        // mode k: the (N - 1 - k)-th smallest eigenvalue (ascending from rocSOLVER): mode 0 the zero one
-        for (int k = 0; k < N; k++) h[4 * N + k] = k == 0 ? 0.0 : lam[N - 1 - k];
-        nsg::launch_dense_mats(dC, dS, 1.0 / std::sqrt(sumhy), N, s->dF, s->dG, s->st);
-        HIPCHK(hipStreamSynchronize(s->st));
-        a.sh0s = std::sqrt(sumhy);   // (mode 0 of the constant 1: sum_j hy_j / sqrt(sum hy))
-    }
-    double* rp0 = h.data() + n_tab;
-    double* bt = rp0 + n_rp0;   // per chunk: beta (the local back substitution over pi) and BR
-    std::vector<double> r(N, 0.0);   // 1 / p of the previous row, per mode
-    std::vector<double> crp((size_t)nsg::FPS_M * N), cpi((size_t)nsg::FPS_M * N);   // this chunk's 1/p, pi
-    const int iend = g.i0 + g.nxl;
-    for (int gi = 0; gi < iend; gi++) {
-        const int li = gi - g.i0;
-        if (li >= 0 && li % nsg::FPS_M == 0)
-            for (int k = 0; k < N; k++) rp0[(size_t)(li / nsg::FPS_M) * ld + k] = r[k];
-        const double pem = gi > 0 ? pe[gi - 1] : 0.0;
-        const int t = li >= 0 ? li % nsg::FPS_M : 0;
-        // (r5: the NEUMANN outflow row eliminated to (-mu / 2, mu): ns_fps.hip piv_next)
-        const bool oe = a.outE && gi == g.nx - 1;
-        for (int k = 0; k < N; k++) {
-            const double gg = (oe ? -0.5 * h[4 * N + k] : pw[gi]) * r[k];
-            const double p = std::fma(-gg, pem, oe ? h[4 * N + k] : -(pw[gi] + pe[gi]) + h[4 * N + k]);   // (piv_next's)
-            r[k] = (k == 0 && gi == g.nx - 1) ? 0.0 : 1.0 / p;
-            if (li >= 0) {
-                crp[(size_t)t * N + k] = r[k];
-                cpi[(size_t)t * N + k] = -gg * (t ? cpi[(size_t)(t - 1) * N + k] : 1.0);
-            }
-        }
-        if (li >= 0 && (t == nsg::FPS_M - 1 || gi == iend - 1)) {   // the chunk's (beta, BR)
-            const int c = li / nsg::FPS_M;
-            for (int k = 0; k < N; k++) {
-                double b = 0.0, R = 1.0;
-                for (int u = t; u >= 0; u--) {
-                    const double rr = crp[(size_t)u * N + k], q = -pe[gi - t + u] * rr;
-                    b = cpi[(size_t)u * N + k] * rr + q * b;
-                    R = q * R;
-                }
-                bt[(size_t)c * ld + k] = b;
-                bt[(size_t)(a.nch + c) * ld + k] = R;
-            }
-        }
-    }
-    // (r5) the pivots tabled for t1b / t2b (ns_fps.hip piv_pair): the recurrence of every mode from global row
-    // 0 over uniform interior rows reaches its fixed point (to 4 ulp) after c_k rows -- many for the low modes,
-    // few for the high ones; whole waves of modes k >= kfast whose c_k are all below prow read 1 / p from
-    // the table there and the converged value after it, instead of one fp64 division per row and mode
-    // (NSGPU_FPS_PTAB=0: divisions everywhere, A/B)
-    std::vector<double> ptab, pinf;
-    std::vector<int> prowb;
-    int prow = 0, kfast = 1 << 30;
-    {
-        // NSGPU_FPS_PTAB: 0 divisions everywhere, 1 the table (A/B), 2 (default) per 128-mode block its fixed-point row
-        const int mode = !s->fps_xuni || s->fps_dense ? 0 : s->k.fps_ptab;   // (r6: stretched -- none)
-        const int PRMAX = std::min(g.nx - 1, mode == 1 ? 1024 : 4096);
-        if (mode != 0 && N > 128 && PRMAX > 64) {
-            std::vector<double> rr(N, 0.0);
-            std::vector<int> conv(N, -1);
-            std::vector<char> left(N, 0);
-            if (mode == 1) ptab.assign((size_t)PRMAX * ld, 0.0);
-            for (int gi = 0; gi < PRMAX; gi++) {
-                const double pem = gi > 0 ? pe[gi - 1] : 0.0;
-                for (int k = 0; k < N; k++) {
-                    const double gg = pw[gi] * rr[k];
-                    const double pv = std::fma(-gg, pem, -(pw[gi] + pe[gi]) + h[4 * N + k]);
-                    const double rn = 1.0 / pv;
-                    // (mode 2: the exact fixed point -- the recurrence returns the same bits from here on, so the
-                    // skipped divisions change nothing; mode 1: within 4 ulp)
-                    const bool fixed = mode == 2 ? rn == rr[k] : std::fabs(rn - rr[k]) <= 4 * 2.220446049250313e-16 * std::fabs(rn);
-                    if (conv[k] < 0 && !left[k] && gi > 1 && fixed) conv[k] = gi;
-                    if (mode == 2 && conv[k] >= 0 && rn != rr[k]) {   // (left it again -- an oscillation: never fast)
-                        conv[k] = -1;
-                        left[k] = 1;
-                    }
-                    rr[k] = rn;
-                    if (mode == 1) ptab[(size_t)gi * ld + k] = rn;
-                }
-            }
-            if (mode == 2) {
-                // (each block's row: the last of its modes to converge, + 1; a block with a mode that did not
-                // converge within PRMAX rows never takes the fixed point)
-                const int nb = (ld + 127) / 128;
-                prowb.assign(nb, 1 << 30);
-                bool any = false;
-                for (int b = 0; b < nb; b++) {
-                    int mx = 0;
-                    bool ok = b * 128 < N;
-                    for (int k = b * 128; k < std::min(N, (b + 1) * 128) && ok; k++) {
-                        ok = conv[k] >= 0;
-                        mx = std::max(mx, conv[k]);
-                    }
-                    if (ok) { prowb[b] = mx + 1; any = true; }
-                }
-                if (any) {
-                    pinf.assign(ld, 0.0);
-                    for (int k = 0; k < N; k++) pinf[k] = rr[k];
-                } else {
-                    prowb.clear();
-                }
-            } else {
-            for (int kf = 128; kf < N; kf += 128) {
-                int mx = 0;
-                bool ok = true;
-                for (int k = kf; k < N && ok; k++) {
-                    ok = conv[k] >= 0;
-                    mx = std::max(mx, conv[k]);
-                }
-                if (ok) {
-                    kfast = kf;
-                    prow = std::min(PRMAX, (mx + 1 + 15) / 16 * 16);
-                    break;
-                }
-            }
-            if (kfast < N) {
-                pinf.assign(ld, 0.0);
-                for (int k = 0; k < N; k++) pinf[k] = rr[k];
-                ptab.resize((size_t)prow * ld);
-            } else {
-                ptab.clear();
-                kfast = 1 << 30;
-            }
-            }
-        }
-    }
-    // (r8) the FIXED chunks of t1b / t2b (FpsArgs::cfix), each condition compared bit for bit on the tables the
-    // device reads: from cfix[b] to clast every chunk of block b starts at the fixed point (rp0 = pinf, and past
-    // prowb so that the general body takes pinf there too), is whole, does not hold global row nx - 1, and its rows
-    // and the row before them share one (pw, pe).  One rank without an outflow side only
-    std::vector<int> cfix;
-    int clast = -1;
+    nsg::FpsTables T;
+    nsg::fps_twiddles(o, T);
+    if (s->fps_dense) CHK(fps_dense_setup(s, hy, T.mu));
+    nsg::fps_chunk_tables(o, T);
+    nsg::fps_pivot_shortcut(o, T);
+    if (NS_FPS_FIXED) nsg::fps_fixed_candidates(o, T);
+    if (P > 1) nsg::fps_mode0_tables(o, T);
+    if (d.og) nsg::fps_rank_aggregates(o, T);
+    // the block, in the kernels' order: the host tables and FpsArgs' work arrays (whole groups' chunks: nchp)
+    const size_t n_c = (size_t)o.nchp() * ld, n_g = (size_t)a.ngrp * ld;
+    d.n = (d.og ? 4 : 2) * (size_t)ld + 8;   // multi-rank: the allgather's own slot and every rank's (d.n each)
     int* d_cfix = nullptr;
-    double* d_fixv = nullptr;
-    if (NS_FPS_FIXED && !prowb.empty() && s->nranks == 1 && g.i0 == 0 && g.nxl == g.nx && !a.outE) {
-        const int nb = (int)prowb.size();
-        auto plain = [&](int c) {   // (the conditions that do not depend on the block)
-            const int gi0 = c * nsg::FPS_M;
-            if (gi0 < 1 || gi0 + nsg::FPS_M > g.nx - 1) return false;
-            for (int gi = gi0; gi < gi0 + nsg::FPS_M; gi++)
-                if (std::memcmp(&pw[gi], &pw[gi0 - 1], sizeof(double)) || std::memcmp(&pe[gi], &pe[gi0 - 1], sizeof(double)))
-                    return false;
-            return true;
-        };
-        for (int c = a.nch - 1; c >= 0 && clast < 0; c--)
-            if (plain(c)) clast = c;
-        cfix.assign(nb, 1 << 30);
-        long nfix = 0;
-        for (int b = 0; b < nb && clast >= 0; b++) {
-            if (prowb[b] >= g.nx) continue;
-            const int k1 = std::min(N, (b + 1) * 128);
-            for (int c = clast; c >= 0; c--) {
-                bool ok = plain(c) && c * nsg::FPS_M >= prowb[b];
-                for (int k = b * 128; k < k1 && ok; k++)
-                    ok = std::memcmp(&rp0[(size_t)c * ld + k], &pinf[k], sizeof(double)) == 0;
-                if (!ok) break;
-                cfix[b] = c;
-            }
-            if (cfix[b] <= clast) nfix += clast - cfix[b] + 1;
-        }
-        if (nfix == 0) cfix.clear();
-    }
-    // (the pivot table and pinf, or pinf and the block rows and first fixed chunks -- ints, in doubles' room)
-    // (r8: and the FIXED chunks' collapsed tables, 3 x ld)
-    const size_t n_pt = !ptab.empty() ? ptab.size() + (size_t)ld : (!prowb.empty() ? (size_t)ld + prowb.size() + 3 * (size_t)ld : 0);
-    // (r5) ny = 16384: e^{-2 pi i m / 8192}, m < 8192, after the pivot table (the two-half transforms)
-    const size_t n_t8 = nsg::fps_log2(N) < 0 ? (size_t)N : 0;
-    HIPCHK(hipMalloc(&s->fps_mem, (total + n_pt + n_t8) * sizeof(double)));
-    HIPCHK(hipMemset(s->fps_mem, 0, (total + n_pt + n_t8) * sizeof(double)));
-    HIPCHK(hipMemcpy(s->fps_mem, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
-    if (n_t8) {
-        std::vector<double> t8(n_t8);
-        for (int m = 0; m < N / 2; m++) {
-            t8[2 * m] = h[4 * m];   // (the 16384-point table's even entries)
-            t8[2 * m + 1] = h[4 * m + 1];
-        }
-        s->fps_tw8 = s->fps_mem + total + n_pt;
-        HIPCHK(hipMemcpy(s->fps_mem + total + n_pt, t8.data(), n_t8 * sizeof(double), hipMemcpyHostToDevice));
-    }
-    if (n_pt && !ptab.empty()) {
-        double* pt = s->fps_mem + total;
-        HIPCHK(hipMemcpy(pt, ptab.data(), ptab.size() * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(pt + ptab.size(), pinf.data(), (size_t)ld * sizeof(double), hipMemcpyHostToDevice));
-        a.ptab = pt;
-        a.pinf = pt + ptab.size();
-        a.prow = prow;
-        a.kfast = kfast;
-    } else if (n_pt) {
-        double* pt = s->fps_mem + total;
-        HIPCHK(hipMemcpy(pt, pinf.data(), (size_t)ld * sizeof(double), hipMemcpyHostToDevice));
-        int* pb = reinterpret_cast<int*>(pt + 4 * (size_t)ld);   // (after pinf and fixv: those are read in pairs)
-        HIPCHK(hipMemcpy(pb, prowb.data(), prowb.size() * sizeof(int), hipMemcpyHostToDevice));
-        a.pinf = pt;
-        a.prowb = pb;
-        d_cfix = pb + prowb.size();
-        d_fixv = pt + ld;
-    }
-    double* d = s->fps_mem;
-    s->fps_tw = d;
-    s->fps_wk = d + 2 * (size_t)N;
-    a.mu = d + 4 * (size_t)N;
-    a.rp0 = d + n_tab;
-    a.bt = d + n_tab + n_rp0;
-    double* q = d + n_tab + n_rp0 + n_bt;
-    a.ga = q; q += 2 * n_g;
-    a.gc = q; q += n_g;
-    a.gb = q; q += 2 * n_g;
-    a.gx = q; q += n_g;
-    a.cb = q; q += 2 * (size_t)nchp * ld;
-    a.ca = q; q += 2 * (size_t)nchp * ld;
-    a.ya = q; q += (size_t)nchp * ld;
-    a.s0 = d + total - 8;   // (r5: the outflow's mode-0 shift, k_fps_mid -> t2b)
-    if (n_mr) {
-        s->fps_ragg = q; q += s->fps_n;
-        s->fps_gath = q; q += (size_t)s->nranks * s->fps_n;
-        // mode 0's response to the constant 1 (r5, the deferred mean): the same recurrences as the kernels
-        // (piv_next, t1b's forward and local back substitution) over f = 1, with mode 0's pivots of the
-        // global rows
-        const int nx = g.nx;
-        std::vector<double> r0(nx);
-        {
-            double rp = 0.0;
-            for (int gi = 0; gi < nx; gi++) {
-                const double gg = pw[gi] * rp, pem = gi > 0 ? pe[gi - 1] : 0.0;
-                const double p = std::fma(-gg, pem, -(pw[gi] + pe[gi]) + 0.0);
-                rp = r0[gi] = gi == nx - 1 ? 0.0 : 1.0 / p;   // (mode 0's pinned last row, a.pin)
-            }
-        }
-        auto fwd = [&](int ga, int gb) {   // forward recurrence from zero over global rows [ga, gb)
-            double E = 0.0;
-            for (int gi = ga; gi < gb; gi++) E = std::fma(-(pw[gi] * (gi > 0 ? r0[gi - 1] : 0.0)), E, 1.0);
-            return E;
-        };
-        std::vector<double> m0((size_t)2 * nchp + a.ngrp + s->nranks, 0.0);
-        for (int c = 0; c < a.nch; c++) {
-            const int gi0 = g.i0 + c * nsg::FPS_M, gi1 = std::min(gi0 + nsg::FPS_M, g.i0 + g.nxl);
-            std::vector<double> y;
-            double E = 0.0;
-            for (int gi = gi0; gi < gi1; gi++) {
-                E = std::fma(-(pw[gi] * (gi > 0 ? r0[gi - 1] : 0.0)), E, 1.0);
-                y.push_back(E);
-            }
-            double xl = 0.0;
-            for (int gi = gi1 - 1; gi >= gi0; gi--) xl = std::fma(y[gi - gi0], r0[gi], -pe[gi] * r0[gi] * xl);
-            m0[c] = E;
-            m0[(size_t)nchp + c] = xl;
-        }
-        for (int gq = 0; gq < a.ngrp; gq++)
-            m0[2 * (size_t)nchp + gq] = fwd(g.i0 + gq * nsg::FPS_G * nsg::FPS_M,
-                                            std::min(g.i0 + (gq + 1) * nsg::FPS_G * nsg::FPS_M, g.i0 + g.nxl));
-        for (int rq = 0; rq < s->nranks; rq++) {
-            int32_t q0, q1;
-            ns_slab_range(g.nx, s->nranks, rq, &q0, &q1);
-            m0[2 * (size_t)nchp + a.ngrp + rq] = fwd(q0, q1);
-        }
-        HIPCHK(hipMemcpy(q, m0.data(), m0.size() * sizeof(double), hipMemcpyHostToDevice));
-        s->m0e = q;
-        s->m0b = q + nchp;
-        s->m0g = q + 2 * (size_t)nchp;
-        s->m0a = s->m0g + a.ngrp;
-        q += m0.size();
-        if (s->fps_og) {
-            // (r5) every rank's backward aggregate (x at its first row, zero carry from the ranks after it) as a
-            // function of its forward carry-in Y: with f = 0, y_i = Y prod(-g), x_i = y_i r_i - pe_i r_i x_{i+1}, so
-            // B_p(k) = sum_i prod_{m <= i}(-g_m) r_i prod_{m < i}(-pe_m r_m) over rank p's rows (piv_next's pivots);
-            // X1_p: mode 0's aggregate of f = 1 from zero (the deferred mean's correction)
-            const int P = s->nranks;
-            std::vector<double> B((size_t)P * ld, 0.0), X1(P, 0.0), rr(N, 0.0), fw(N), bw(N);
-            int rq = 0;
-            int32_t q0 = 0, q1 = 0;
-            ns_slab_range(nx, P, 0, &q0, &q1);
-            double y1 = 0.0, bw1 = 1.0;
-            for (int gi = 0; gi < nx; gi++) {
-                while (gi >= q1) { rq++; ns_slab_range(nx, P, rq, &q0, &q1); }
-                if (gi == q0) {
-                    std::fill(fw.begin(), fw.end(), 1.0);
-                    std::fill(bw.begin(), bw.end(), 1.0);
-                    y1 = 0.0;
-                    bw1 = 1.0;
-                }
-                const double pem = gi > 0 ? pe[gi - 1] : 0.0;
-                double* Bq = B.data() + (size_t)rq * ld;
-                const bool oe = a.outE && gi == nx - 1;   // (r6: the eliminated outflow row, piv_next)
-                for (int k = 0; k < N; k++) {
-                    const double gg = (oe ? -0.5 * h[4 * N + k] : pw[gi]) * rr[k];
-                    const double p = std::fma(-gg, pem, oe ? h[4 * N + k] : -(pw[gi] + pe[gi]) + h[4 * N + k]);
-                    rr[k] = (k == 0 && gi == nx - 1) ? 0.0 : 1.0 / p;
-                    fw[k] *= -gg;
-                    Bq[k] += fw[k] * rr[k] * bw[k];
-                    bw[k] *= -pe[gi] * rr[k];
-                }
-                // (mode 0, f = 1: y_i = 1 - g_i y_{i-1}, the same back substitution)
-                y1 = std::fma(-(pw[gi] * (gi > 0 ? r0[gi - 1] : 0.0)), y1, 1.0);
-                X1[rq] += y1 * r0[gi] * bw1;
-                bw1 *= -pe[gi] * r0[gi];
-            }
-            HIPCHK(hipMemcpy(q, B.data(), B.size() * sizeof(double), hipMemcpyHostToDevice));
-            s->og_b = q;
-            q += B.size();
-            HIPCHK(hipMemcpy(q, X1.data(), X1.size() * sizeof(double), hipMemcpyHostToDevice));
-            s->og_x1 = q;
-            q += X1.size();
-        }
-    }
-    a.pw = s->c.pw;
-    a.pe = s->c.pe;
-    // (r8) the FIXED chunks' tables collapsed to one row per block (FpsArgs::fixv): P from a run of k_fps_t1b itself
-    // (its general body on every chunk, a zero plane -- P is the operator's), beta and BR from bt; every FIXED chunk's
-    // row must equal its block's first bit for bit, or the block has no FIXED chunks
+    double* d_fixv = nullptr;   // (r8: the FIXED chunks' first chunks and collapsed tables, filled by fps_fixed_check)
+    Arena A;
+    A.add(d.tw, T.tw); A.add(d.wk, T.wk); A.add(a.mu, T.mu); A.add(a.rp0, n_c, T.rp0()); A.add(a.bt, 2 * n_c, T.bt());
+    A.add(a.ga, 2 * n_g); A.add(a.gc, n_g); A.add(a.gb, 2 * n_g); A.add(a.gx, n_g);
+    A.add(a.cb, 2 * n_c); A.add(a.ca, 2 * n_c); A.add(a.ya, n_c);
+    A.add(d.ragg, P > 1 ? d.n : 0); A.add(d.gath, P > 1 ? (size_t)P * d.n : 0);
+    A.add(d.m0e, T.m0e); A.add(d.m0b, T.m0b); A.add(d.m0g, T.m0g); A.add(d.m0a, T.m0a);
+    A.add(d.og_b, T.ogb); A.add(d.og_x1, T.ogx1);
+    A.add(a.s0, 8); A.add(a.ptab, T.ptab); A.add(a.pinf, T.pinf);   // (r5, s0: the outflow's mode-0 shift, k_fps_mid -> t2b)
+    A.add(d_fixv, T.prowb.empty() ? 0 : 3 * (size_t)ld); A.add(a.prowb, T.prowb); A.add(d_cfix, T.prowb.size());
+    A.add(d.tw8, T.tw8);
+    const size_t bytes = A.place(nullptr);
+    HIPCHK(hipMalloc(&d.mem, bytes));
+    HIPCHK(hipMemset(d.mem, 0, bytes));
+    A.place(reinterpret_cast<char*>(d.mem));
+    HIPCHK(A.upload());
+    if (a.ptab) { a.prow = T.prow; a.kfast = T.kfast; }
+    a.pw = s->c.pw; a.pe = s->c.pe;
     long nfix = 0;
-    if (!cfix.empty() && d_cfix) {
-        const size_t npl = (size_t)g.nxl * ld, nP = (size_t)a.nch * ld;
-        double* zero = nullptr;
-        HIPCHK(hipMalloc(&zero, npl * sizeof(double)));
-        HIPCHK(hipMemsetAsync(zero, 0, npl * sizeof(double), s->st));
-        nsg::launch_fps_t1b(a, zero, s->st);
-        std::vector<double> hP(nP);
-        HIPCHK(hipMemcpyAsync(hP.data(), a.ca + nP, nP * sizeof(double), hipMemcpyDeviceToHost, s->st));
-        HIPCHK(hipStreamSynchronize(s->st));
-        HIPCHK(hipFree(zero));
-        std::vector<double> fv(3 * (size_t)ld, 0.0);
-        const double* tab[3] = {hP.data(), bt, bt + nP};
-        for (int b = 0; b < (int)cfix.size(); b++) {
-            if (cfix[b] > clast) continue;
-            const int k0 = b * 128, nk = std::min(N, k0 + 128) - k0;
-            bool ok = true;
-            for (int q = 0; q < 3 && ok; q++) {
-                const double* row0 = tab[q] + (size_t)cfix[b] * ld + k0;
-                std::memcpy(&fv[(size_t)q * ld + k0], row0, nk * sizeof(double));
-                for (int c = cfix[b] + 1; c <= clast && ok; c++)
-                    ok = std::memcmp(tab[q] + (size_t)c * ld + k0, row0, nk * sizeof(double)) == 0;
-            }
-            if (ok) nfix += clast - cfix[b] + 1;
-            else cfix[b] = 1 << 30;
-        }
-        if (nfix > 0) {
-            HIPCHK(hipMemcpy(d_fixv, fv.data(), fv.size() * sizeof(double), hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(d_cfix, cfix.data(), cfix.size() * sizeof(int), hipMemcpyHostToDevice));
-            a.cfix = d_cfix;
-            a.clast = clast;
-            a.fixv = d_fixv;
-        }
-    }
+    CHK(fps_fixed_check(s, o, T, d_cfix, d_fixv, &nfix));
     if (s->k.verbose && s->rank == 0) {
-        const int nbm = (N + 127) / 128;
+        const int nbm = (g.ny + 127) / 128;
         fprintf(stderr, "nsgpu fps: fixed chunks %ld of %ld (block, chunk) pairs", nfix, (long)nbm * a.nch);
         if (nfix > 0) {
-            fprintf(stderr, " (%d x %d, last fixed chunk %d); fixed-point rows:", nbm, a.nch, clast);
-            for (int b = 0; b < nbm; b++) fprintf(stderr, prowb[b] >= g.nx ? " -" : " %d", prowb[b]);
+            fprintf(stderr, " (%d x %d, last fixed chunk %d); fixed-point rows:", nbm, a.nch, T.clast);
+            for (int b = 0; b < nbm; b++) fprintf(stderr, T.prowb[b] >= g.nx ? " -" : " %d", T.prowb[b]);
             fprintf(stderr, "; first fixed chunks:");
-            for (int b = 0; b < nbm; b++) fprintf(stderr, cfix[b] > clast ? " -" : " %d", cfix[b]);
+            for (int b = 0; b < nbm; b++) fprintf(stderr, T.cfix[b] > T.clast ? " -" : " %d", T.cfix[b]);
         }
         fprintf(stderr, "\n");
     }
@@ -3257,7 +2998,7 @@ bool fps_checks_next(const ns_solver* s) {
 // the (sum, sum^2) partials of rhs_phi -> the sums and the null-space shift (one rank: one launch)
 int div_mean(ns_solver* s, int nb) {
     if (s->mean_pend) {   // (r5) the sums ride on the direct solve's forward allgather (fps_scan)
-        nsg::launch_reduce_sum(s->part, nb, 2, s->fps_ragg + 2 * (size_t)s->g.ld, s->st);
+        nsg::launch_reduce_sum(s->part, nb, 2, s->fpd.ragg + 2 * (size_t)s->g.ld, s->st);
         return 0;
     }
     if (!comm_on(s)) {
@@ -3281,7 +3022,7 @@ int divergence_fps(ns_solver* s) {
     double* b = fps_checks_next(s) ? s->arr[NS_ARR_RPHI] : nullptr;
     auto launch = [&](int phase) {
         return nsg::launch_fps_div(s->k, s->g, s->c, s->dt, s->arr[NS_ARR_U], s->arr[NS_ARR_V], b, s->arr[NS_ARR_TMP],
-                                   s->part, phase, s->fps_tw, s->fps_wk, s->st, s->fa.outE);
+                                   s->part, phase, s->fpd.tw, s->fpd.wk, s->st, s->fa.outE);
     };
     const HaloReq r[2] = {{&s->g, s->arr[NS_ARR_U], 1}, {&s->g, s->arr[NS_ARR_V], 1}};
     int nb;
@@ -4169,7 +3910,7 @@ int create_solvers(ns_solver* s, const ns_grid_desc* gd, const ns_params* p) {
     if (s->fps || s->fps_pc) CHK(fps_setup(s, hy0, h.data(), h.data() + g.nx));
     // (r6: the deferred mean not with an outflow side -- its mode 0 takes the projected shift, the mean never enters;
     // m0e: fps_setup built the mode-0 tables)
-    s->fps_defer = s->bus && s->fps && s->fps_fuse && s->m0e && !s->fa.outE && s->k.fps_defer;
+    s->fps_defer = s->bus && s->fps && s->fps_fuse && s->fpd.m0e && !s->fa.outE && s->k.fps_defer;
     // a masked domain's Poisson preconditioner: one V-cycle of the BOUNDING BOX's wall-closure
     // multigrid (a fictitious-domain preconditioner: the rhs is 0 outside the domain, the
     // outside values of the result are ignored by the masked operator), unless preconditioned by the box's
@@ -4405,8 +4146,8 @@ void ns_destroy(ns_solver* s) {
     if (s->kv_mem) (void)hipFree(s->kv_mem);
     if (s->cvimg) (void)hipFree(s->cvimg);
     if (s->dmat) (void)hipFree(s->dmat);
-    if (s->fps_mem) (void)hipFree(s->fps_mem);
-    if (s->dense_mem) (void)hipFree(s->dense_mem);
+    if (s->fpd.mem) (void)hipFree(s->fpd.mem);
+    if (s->fpd.dense_mem) (void)hipFree(s->fpd.dense_mem);
     if (s->rb) (void)dense_lib().destroy(s->rb);
     if (s->cap_mem) (void)hipFree(s->cap_mem);
     if (s->f32_mem) (void)hipFree(s->f32_mem);
