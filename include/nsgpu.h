@@ -330,6 +330,38 @@ int  ns_scalar_buoyancy(ns_solver* s, const ns_buoyancy_desc* d);
  * Additive to ABI 9. */
 int  ns_edge_profile(ns_solver* s, int32_t edge, const double* info, int32_t n);
 
+/* ---- derived fields on the device: pressure, vorticity, divergence, stream function ----
+ * From the current u, v, phi, between steps ("Derived fields"; the normative statement is
+ * tests/derived_ref.py).  Face values are Div_V's: r-weighted toward a neighbour in the domain, 0.5 (q + ghost) on a
+ * boundary face with that edge's velocity ghost (its profile entry where ns_edge_profile set one).
+ *   div  = (u_E - u_W) / hx + (v_N - v_S) / hy          what the approximate projection leaves (K3 without 1 / dt)
+ *   vort = (v_E - v_W) / hx - (u_N - u_S) / hy
+ *   p    = phi - dt / (2 re) L phi                       ExportData's pressure (L: LHS_phi with its NEUMANN rows)
+ *   psi  at the (nx + 1) x (ny + 1) cell vertices, i outer: the volume flux through the vertical line from the box's
+ *        bottom to the vertex -- psi(0, 0) = 0, psi(i + 1, 0) = psi(i, 0) - v_S(i, 0) hx[i], psi(i, j + 1) =
+ *        psi(i, j) + u_face(i, j) hy[j].  A flux function, not a Poisson solve: path-independent only up to the
+ *        column's accumulated div * area.
+ * ns_derived: host buffers, NULL = not wanted (and not stored on the device); p, vort, div are nx_local x ny
+ * bounding-box planes as ns_get_array's, exactly 0 outside a polygon.  With all four NULL (or out == NULL) the call
+ * is a stats-only pass.  A deferred correction (ns_step_async) is settled first, as by ns_get_array; the call runs
+ * on the solver's stream, writes no NS_ARR_* plane and none of the step's partial / scalar slots, and keeps the
+ * Poisson guess history.  Its device planes are allocated on first use, only those ever asked for (not counted by
+ * ns_device_bytes).  NS_EINVAL for a null solver, out and st both NULL, and nranks > 1.  Additive to ABI 9. */
+typedef struct ns_derived {
+    double* p; double* vort; double* div;
+    double* psi;
+} ns_derived;
+typedef struct ns_derived_stats {
+    double  ke, enstrophy;       /* 1/2 sum A (u^2 + v^2), 1/2 sum A vort^2 over the domain's cells, A = hx hy */
+    double  div_l2, div_max;     /* sqrt(sum A div^2), max |div| */
+    double  cfl;                 /* dt max(|u| / hx + |v| / hy) */
+    double  vort_min, vort_max, p_min, p_max;
+    double  psi_min, psi_max;    /* NaN when psi was not asked for */
+    double  t_kernel_ms;         /* the cell pass (timing == 1) */
+    int32_t n_kernels;
+} ns_derived_stats;
+int  ns_derive(ns_solver* s, const ns_derived* out, ns_derived_stats* st);   /* either may be NULL, not both */
+
 /* ---- host-side helpers (no GPU needed) ---- */
 /* the face averages of the parabola 6 s (1 - s) * mean over the faces k0 <= k < k1 of spacings h[0..n) (s runs 0..1
  * from face k0's lower end to face k1-1's upper end), 0 elsewhere: the average over [sa, sb] is

@@ -104,6 +104,22 @@ class NsBuoyancyDesc(ctypes.Structure):
     _fields_ = [("bx", ctypes.c_double), ("by", ctypes.c_double), ("tref", ctypes.c_double)]
 
 
+class NsDerived(ctypes.Structure):
+    _fields_ = [("p", ctypes.POINTER(ctypes.c_double)), ("vort", ctypes.POINTER(ctypes.c_double)),
+                ("div", ctypes.POINTER(ctypes.c_double)), ("psi", ctypes.POINTER(ctypes.c_double))]
+
+
+class NsDerivedStats(ctypes.Structure):
+    _fields_ = [("ke", ctypes.c_double), ("enstrophy", ctypes.c_double), ("div_l2", ctypes.c_double),
+                ("div_max", ctypes.c_double), ("cfl", ctypes.c_double), ("vort_min", ctypes.c_double),
+                ("vort_max", ctypes.c_double), ("p_min", ctypes.c_double), ("p_max", ctypes.c_double),
+                ("psi_min", ctypes.c_double), ("psi_max", ctypes.c_double), ("t_kernel_ms", ctypes.c_double),
+                ("n_kernels", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _P = ctypes.c_void_p
 _D = ctypes.POINTER(ctypes.c_double)
 SIGNATURES = {
@@ -131,6 +147,7 @@ SIGNATURES = {
     "ns_scalar_get_rhs": (ctypes.c_int, [_P, _D]),
     "ns_scalar_buoyancy": (ctypes.c_int, [_P, ctypes.POINTER(NsBuoyancyDesc)]),
     "ns_edge_profile": (ctypes.c_int, [_P, ctypes.c_int32, _D, ctypes.c_int32]),
+    "ns_derive": (ctypes.c_int, [_P, ctypes.POINTER(NsDerived), ctypes.POINTER(NsDerivedStats)]),
     "ns_parabolic_profile": (ctypes.c_int, [_D, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, _D]),
     "ns_slab_range": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                      ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),

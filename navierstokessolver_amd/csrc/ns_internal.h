@@ -134,6 +134,23 @@ int launch_rhs_t(const Knobs& kn, const Geo& g, const Coef& c, const int* tneu, 
                  hipStream_t st, const Buoy* by = nullptr);
 // (min, -max) partials of a plane's own cells, 2 per block (launch_reduce_min's layout)
 int launch_minmax(const Geo& g, const double* f, double* part, hipStream_t st);
+// derived fields (ns_derive; DESIGN.md 4, "Derived fields"): one rank only (-1 otherwise).
+// launch_derived, the cell pass: P = phi - alpha L phi, vorticity, divergence of every domain cell into op / ow / od
+// (each may be null: not stored; rows of g.ld doubles from local row 0, exactly 0 outside a masked domain) -- the
+// rectangle's streaming strips (k_derived_s), or thread per cell (k_derived_grid: masked domains, a rectangle with an
+// edge profile, NSGPU_CELL=grid).
+// part: 9 derived_partials(g) doubles -- per block / strip 3 sums (A (u^2 + v^2), A w^2, A d^2), then 4 minima
+// (-|d|, -(|u| / hx + |v| / hy), w, -w), then 2 (p, -p); the count is returned
+int derived_partials(const Geo& g);
+int launch_derived(const Knobs& kn, const Geo& g, const Coef& c, double alpha, const double* u, const double* v,
+                   const double* phi, double* op, double* ow, double* od, double* part, hipStream_t st);
+// the stream function at the (nx + 1) x (ny + 1) vertices (rows of ldv doubles): k_psi_base (base: nx + 1 doubles,
+// psi(i, 0)) and k_psi_scan; (min, -max) per vertex row at part (2 (nx + 1) doubles); the row count is returned
+int launch_psi(const Geo& g, const Coef& c, const double* u, const double* v, double* base, double* psi, int ldv,
+               double* part, hipStream_t st);
+// the n cell-pass partials (blocks of capacity ncap, launch_derived's layout) and psi's np rows -> out[0..11): the 3
+// sums, the 4 + 2 minima, psi's (min, -max) (np = 0: +inf)
+void launch_derived_reduce(const double* part, int n, int ncap, const double* pp, int np, double* out, hipStream_t st);
 // K2: fused red-black SOR sweep of (I - a L_V) on u and v, (u,v) -> (uo,vo);
 //     residual^2 partials of the input if part != null: u at part[0..n), v at part[n..2n), n returned
 int launch_helm_sweep(const Knobs& kn, const Geo& g, const Coef& c, double alpha, double omega, const double* u, const double* v,

@@ -2671,6 +2671,393 @@ __global__ __launch_bounds__(256) void k_cell_s(CellStreamArgs A) {
         for (int k = 0; k < NV; k++) A.part[NV * wid + k] = acc[k];
 }
 
+// ------------------------------------------------ derived fields (ns_derive; DESIGN.md 4, "Derived fields")
+// Pressure P = phi - alpha L phi (ExportData; L: k_apply<0, Topo>'s rows), vorticity and the divergence the
+// approximate projection leaves, all from Div_V's face values (face_val: r-weighted toward a neighbour in the
+// domain, 0.5 (q + ghost) with the edge's velocity ghost on a boundary face), and the domain integrals a run is
+// watched by.  The products and sums a compiler may contract live in the dv_* helpers with contraction off, and
+// every form -- the strips and the thread-per-cell kernel -- goes through them: they agree bit for bit.
+__device__ __forceinline__ double dv_face(double q, double qn, double r) {
+#pragma clang fp contract(off)
+    return qn * r + q * (1 - r);
+}
+__device__ __forceinline__ double dv_wall(double q, double ghost) {
+#pragma clang fp contract(off)
+    return 0.5 * (q + ghost);
+}
+// 1 / h: once per row and per column (dv_rcp), not a division per difference -- the strips are bound by their
+// arithmetic, not by HBM, with four fp64 divisions per cell
+__device__ __forceinline__ double dv_rcp(double h) {
+#pragma clang fp contract(off)
+    return 1.0 / h;
+}
+// (a1 - a0) rhx + sg (b1 - b0) rhy: the divergence (sg = 1) and the vorticity (sg = -1)
+__device__ __forceinline__ double dv_diff(double a1, double a0, double rhx, double b1, double b0, double rhy, double sg) {
+#pragma clang fp contract(off)
+    return (a1 - a0) * rhx + sg * ((b1 - b0) * rhy);
+}
+__device__ __forceinline__ double dv_lap_nb(double s, double w, double xn, double xc) {
+#pragma clang fp contract(off)
+    return s + w * (xn - xc);
+}
+// a NEUMANN face: (ghost - x_c) w2, w2 = (1 / h)^2 (dv_rsq of dv_rcp), with the ghost 2.5 x_c - 2 x_1 + 0.5 x_2 (x_1, x_2 inward)
+__device__ __forceinline__ double dv_rsq(double rh) {
+#pragma clang fp contract(off)
+    return rh * rh;
+}
+__device__ __forceinline__ double dv_lap_neu(double s, double w2, double xc, double x1, double x2) {
+#pragma clang fp contract(off)
+    const double gh = 2.5 * xc - 2.0 * x1 + 0.5 * x2;
+    return s + (gh - xc) * w2;
+}
+__device__ __forceinline__ double dv_press(double pc, double alpha, double s) {
+#pragma clang fp contract(off)
+    return pc - alpha * s;
+}
+__device__ __forceinline__ double dv_mul(double a, double b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+// NaN-propagating min (a blown-up field is visible in the stats, as K5's monitor)
+__device__ __forceinline__ double dv_min(double a, double x) { return fmin(a, x != x ? -INFINITY : x); }
+
+// one cell's P, vorticity, divergence: U / V / P(di, dj) give u, v, phi at that offset (global loads, or a strip's
+// register windows and lane neighbours; P also at +-2 along the normal of a NEUMANN face)
+// X(t) / Y(t): table t of the cell's row / column -- 0: h, 1 / 2: the face weight toward the lower / upper neighbour
+// (Coef::fwx / fex, fsy / fny), 3 / 4: the Poisson weight toward it (pw / pe, ps / pn), 5: dv_rcp(h) -- global tables
+// or a strip's registers
+// SEL (the strips: every accessor a register, every ghost arithmetic): both sides of each face are evaluated and
+// selected, no branch; otherwise a neighbour or a ghost is read only where the face has one
+template <class T, bool SEL, class FU, class FV, class FP, class FX, class FY>
+__device__ __forceinline__ void derived_cell(const Geo& g, double alpha, FU&& U, FV&& V, FP&& P, FX&& X, FY&& Y, int li,
+                                             int j, double& p_, double& w_, double& d_) {
+    const T t(g, li, j);
+    const bool hW = t.in(-1, 0), hE = t.in(1, 0), hS = t.in(0, -1), hN = t.in(0, 1);
+    const double fw = X(1), fe = X(2), fs = Y(1), fn = Y(2);
+    const double uc = U(0, 0), vc = V(0, 0), pc = P(0, 0);
+    // the value of component d (q at the cell, Q its accessor) on face k (toward (di, dj), weight r)
+    auto face = [&](bool has, double q, auto& Q, int di, int dj, double r, int k, int d) {
+        if (SEL) {
+            const double a = dv_face(q, Q(di, dj), r), b = dv_wall(q, t.gv(0, 0, k, q, d));
+            return has ? a : b;
+        }
+        return has ? dv_face(q, Q(di, dj), r) : dv_wall(q, t.gv(0, 0, k, q, d));
+    };
+    // x-faces: u for the divergence (component 0's ghost), v for the vorticity (component 1's); y-faces likewise
+    const double uW = face(hW, uc, U, -1, 0, fw, 0, 0), uE = face(hE, uc, U, 1, 0, fe, 1, 0);
+    const double vW = face(hW, vc, V, -1, 0, fw, 0, 1), vE = face(hE, vc, V, 1, 0, fe, 1, 1);
+    const double uS = face(hS, uc, U, 0, -1, fs, 2, 0), uN = face(hN, uc, U, 0, 1, fn, 3, 0);
+    const double vS = face(hS, vc, V, 0, -1, fs, 2, 1), vN = face(hN, vc, V, 0, 1, fn, 3, 1);
+    const double rhx = X(5), rhy = Y(5);
+    d_ = dv_diff(uE, uW, rhx, vN, vS, rhy, 1.0);
+    w_ = dv_diff(vE, vW, rhx, uN, uS, rhy, -1.0);
+    // k_apply<0, Topo>'s sum in its order (W, E, S, N): toward (di, dj) with the weight pw, or across a boundary face
+    // -- 0 on a wall / inlet, the extrapolated ghost's term on a NEUMANN one (x_1, x_2 inward)
+    auto lap = [&](double s, bool has, int di, int dj, double pw, double rh, int k) {
+        if (SEL) {
+            const double a = dv_lap_nb(s, pw, P(di, dj), pc), b = dv_lap_neu(s, dv_rsq(rh), pc, P(-di, -dj), P(-2 * di, -2 * dj));
+            return has ? a : t.edge(k).neu ? b : s;
+        }
+        if (has) return dv_lap_nb(s, pw, P(di, dj), pc);
+        return t.edge(k).neu ? dv_lap_neu(s, dv_rsq(rh), pc, P(-di, -dj), P(-2 * di, -2 * dj)) : s;
+    };
+    double s = 0.0;
+    s = lap(s, hW, -1, 0, X(3), rhx, 0);
+    s = lap(s, hE, 1, 0, X(4), rhx, 1);
+    s = lap(s, hS, 0, -1, Y(3), rhy, 2);
+    s = lap(s, hN, 0, 1, Y(4), rhy, 3);
+    p_ = dv_press(pc, alpha, s);
+}
+
+// a cell's terms of the integrals: sums (A (u^2 + v^2), A w^2, A d^2), minima (-|d|, -(|u| / hx + |v| / hy), w, -w)
+// and (p, -p); rhx, rhy = 1 / hx, 1 / hy
+__device__ __forceinline__ void derived_acc(double hx, double hy, double rhx, double rhy, double uc, double vc, double p,
+                                            double w, double d, double (&as)[3], double (&am)[4], double (&ap)[2]) {
+    const double A = dv_mul(hx, hy);
+    as[0] += dv_mul(A, dv_mul(uc, uc) + dv_mul(vc, vc));
+    as[1] += dv_mul(A, dv_mul(w, w));
+    as[2] += dv_mul(A, dv_mul(d, d));
+    am[0] = dv_min(am[0], -fabs(d));
+    am[1] = dv_min(am[1], -(dv_mul(fabs(uc), rhx) + dv_mul(fabs(vc), rhy)));
+    am[2] = dv_min(am[2], w);
+    am[3] = dv_min(am[3], -w);
+    ap[0] = dv_min(ap[0], p);
+    ap[1] = dv_min(ap[1], -p);
+}
+
+// the thread-per-cell form: every masked domain, the rectangle under NSGPU_CELL=grid, the strips' equivalence
+// oracle.  op / ow / od: the planes asked for (null: not stored; rows of g.ld doubles from local row 0), exactly 0
+// outside the domain.  Partials per block: 3 sums at ps, 4 + 2 minima at pa / pb
+template <class T>
+__global__ __launch_bounds__(256) void k_derived_grid(Geo g, Coef c, double alpha, const double* __restrict__ u,
+                                                      const double* __restrict__ v, const double* __restrict__ phi,
+                                                      double* __restrict__ op, double* __restrict__ ow,
+                                                      double* __restrict__ od, double* __restrict__ ps,
+                                                      double* __restrict__ pa, double* __restrict__ pb, int rows) {
+    const int j = blockIdx.x * 64 + threadIdx.x;
+    const int lend = min((int)(blockIdx.y + 1) * 4 * rows, g.nxl);
+    double as[3] = {0.0, 0.0, 0.0}, am[4] = {INFINITY, INFINITY, INFINITY, INFINITY}, ap[2] = {INFINITY, INFINITY};
+    for (int li = blockIdx.y * 4 * rows + threadIdx.y; li < lend && j < g.ny; li += 4) {
+        const ptrdiff_t o = (ptrdiff_t)li * g.ld + j;
+        if (!T(g, li, j).cell()) {
+            if (op) op[o] = 0.0;
+            if (ow) ow[o] = 0.0;
+            if (od) od[o] = 0.0;
+            continue;
+        }
+        auto U = [&](int di, int dj) { return u[o + (ptrdiff_t)di * g.ld + dj]; };
+        auto V = [&](int di, int dj) { return v[o + (ptrdiff_t)di * g.ld + dj]; };
+        auto P = [&](int di, int dj) { return phi[o + (ptrdiff_t)di * g.ld + dj]; };
+        const int gi = g.i0 + li;
+        auto X = [&](int t) { return t == 0 ? c.hx[gi] : t == 1 ? c.fwx[gi] : t == 2 ? c.fex[gi] : t == 3 ? c.pw[gi] : t == 4 ? c.pe[gi] : dv_rcp(c.hx[gi]); };
+        auto Y = [&](int t) { return t == 0 ? c.hy[j] : t == 1 ? c.fsy[j] : t == 2 ? c.fny[j] : t == 3 ? c.ps[j] : t == 4 ? c.pn[j] : dv_rcp(c.hy[j]); };
+        double p, w, d;
+        derived_cell<T, false>(g, alpha, U, V, P, X, Y, li, j, p, w, d);
+        if (op) op[o] = p;
+        if (ow) ow[o] = w;
+        if (od) od[o] = d;
+        derived_acc(c.hx[gi], c.hy[j], X(5), Y(5), u[o], v[o], p, w, d, as, am, ap);
+    }
+    const int b = blockIdx.x + gridDim.x * blockIdx.y;
+    block_reduce_sum<3>(as, ps + 3 * b);
+    block_reduce_min<4>(am, pa + 4 * b);
+    block_reduce_min<2>(ap, pb + 2 * b);
+}
+
+// the rectangle's strip walk, in k_cell_s's shape: a wave owns 128 columns (2 per lane, 16-byte loads) and writes
+// 124, u, v and phi each in a 3-row register window (rows ib - 1 .. ie, prefetched DV_SD ahead), y-neighbours from
+// the adjacent lanes, the wall faces through the ghosts in the strip; a NEUMANN x side loads one extra phi row (K7).
+// u, v, phi are read once (24 B/cell), only the planes asked for are stored, the integrals' partials per strip
+struct DerivedStreamArgs {
+    Geo g;
+    Coef c;
+    double alpha;
+    const double *u, *v, *phi;
+    double *op, *ow, *od;
+    double *ps, *pa, *pb;
+    int nsj;
+    RowPlan P;
+};
+#ifndef DV_SD
+#define DV_SD 3
+#endif
+// (167 VGPRs at three waves per SIMD, no scratch; without the bound the allocator settles at 169 and two waves.  A
+// rectangle with an edge profile takes the thread-per-cell form: the strips' profiled instantiation -- a table test
+// per ghost -- needs 187 VGPRs and spills)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k_derived_s(DerivedStreamArgs A) {
+    const Geo& g = A.g;
+    const Coef& c = A.c;
+    const int lane = threadIdx.x & 63;
+    const int nstr = A.nsj * A.P.nrun;
+    const int w = __builtin_amdgcn_readfirstlane(xcd_swizzle(blockIdx.x, gridDim.x) * 4 + (int)(threadIdx.x >> 6));
+    double as[3] = {0.0, 0.0, 0.0}, am[4] = {INFINITY, INFINITY, INFINITY, INFINITY}, ap[2] = {INFINITY, INFINITY};
+    if (w < nstr) {
+        const int run = w / A.nsj, sj = w - run * A.nsj;
+        int ib, ie;
+        A.P.rows(run, ib, ie);
+        const int jb = sj * SW;
+        const int ny = g.ny, ld = g.ld;
+        const int c0 = jb - 2 + 2 * lane, c1 = c0 + 1;
+        const int lc = min(max(c0, 0), ld - 2);
+        const int k0 = min(max(c0, 0), ny - 1), k1 = min(max(c1, 0), ny - 1);
+        // the columns' tables (h, the face weights, the Poisson weights), once per strip
+        const double ya[6] = {c.hy[k0], c.fsy[k0], c.fny[k0], c.ps[k0], c.pn[k0], dv_rcp(c.hy[k0])};
+        const double yb[6] = {c.hy[k1], c.fsy[k1], c.fny[k1], c.ps[k1], c.pn[k1], dv_rcp(c.hy[k1])};
+        const int rlo = -HALO, rhi = g.nxl + HALO - 1;
+        double2 U0 = {0, 0}, U1 = {0, 0}, U2 = {0, 0}, V0 = {0, 0}, V1 = {0, 0}, V2 = {0, 0};
+        double2 P0 = {0, 0}, P1 = {0, 0}, P2 = {0, 0};
+        double2 QU[DV_SD], QV[DV_SD], QP[DV_SD];
+        auto load = [&](int r, double2& qu, double2& qv, double2& qp) {
+            const ptrdiff_t o = (ptrdiff_t)min(max(r, max(ib - 1, rlo)), min(ie, rhi)) * ld + lc;
+            qu = *reinterpret_cast<const double2*>(A.u + o);
+            qv = *reinterpret_cast<const double2*>(A.v + o);
+            qp = *reinterpret_cast<const double2*>(A.phi + o);
+        };
+        auto step = [&](const double2 qu, const double2 qv, const double2 qp, int r) {
+            U0 = U1; U1 = U2; U2 = qu;
+            V0 = V1; V1 = V2; V2 = qv;
+            P0 = P1; P1 = P2; P2 = qp;
+            const int m = r - 1;
+            if (m < ib || m >= ie) return;
+            const int gi = g.i0 + m;
+            // the lanes' column predicates (existence of the y-neighbours, what is stored and summed) are formed
+            // again per row from this copy: hoisted out of the row loop each lives in an SGPR pair, and the kernel
+            // then spills SGPRs
+            int cc = c0;
+            asm volatile("" : "+v"(cc));
+            const bool v0 = cc >= 0 && cc < ny, v1 = cc + 1 >= 0 && cc + 1 < ny;
+            const bool wr = cc >= jb && cc < jb + SW && cc < ny;
+            const bool o0 = wr && v0, o1 = wr && v1;
+            const int k0 = min(max(cc, 0), ny - 1), k1 = min(max(cc + 1, 0), ny - 1);
+            // the columns c0 - 1 and c1 + 1 of u, v, phi, and c0 - 2, c1 + 2 of phi (a NEUMANN y side's ghost)
+            const double us0 = lane_up1(U1.y), un1 = lane_dn1(U1.x);
+            const double vs0 = lane_up1(V1.y), vn1 = lane_dn1(V1.x);
+            const double ps0 = lane_up1(P1.y), pn1 = lane_dn1(P1.x);
+            const double ps1 = lane_up1(P1.x), pn2 = lane_dn1(P1.y);
+            // row m + 2 (W side) or m - 2 (E side) of a NEUMANN x side
+            double2 X2 = {0.0, 0.0};
+            const bool nW = gi == 0 && g.neu[0], nE = gi == g.nx - 1 && g.neu[1];
+            if (nW || nE) X2 = *reinterpret_cast<const double2*>(A.phi + (ptrdiff_t)(nW ? m + 2 : m - 2) * ld + lc);
+            const double xr[6] = {c.hx[gi], c.fwx[gi], c.fex[gi], c.pw[gi], c.pe[gi], dv_rcp(c.hx[gi])};   // (the row's: wave-uniform)
+            auto X = [&](int t) { return xr[t]; };
+            double p[2], wv[2], d[2];
+#pragma unroll
+            for (int e = 0; e < 2; e++) {
+                auto Y = [&](int t) { return e ? yb[t] : ya[t]; };
+                auto U = [&](int di, int dj) {
+                    return di < 0 ? (e ? U0.y : U0.x) : di > 0 ? (e ? U2.y : U2.x)
+                         : dj < 0 ? (e ? U1.x : us0) : dj > 0 ? (e ? un1 : U1.y) : (e ? U1.y : U1.x);
+                };
+                auto V = [&](int di, int dj) {
+                    return di < 0 ? (e ? V0.y : V0.x) : di > 0 ? (e ? V2.y : V2.x)
+                         : dj < 0 ? (e ? V1.x : vs0) : dj > 0 ? (e ? vn1 : V1.y) : (e ? V1.y : V1.x);
+                };
+                auto P = [&](int di, int dj) {
+                    return di == -2 || di == 2 ? (e ? X2.y : X2.x)
+                         : di < 0 ? (e ? P0.y : P0.x) : di > 0 ? (e ? P2.y : P2.x)
+                         : dj == -2 ? (e ? ps0 : ps1) : dj == 2 ? (e ? pn2 : pn1)
+                         : dj < 0 ? (e ? P1.x : ps0) : dj > 0 ? (e ? pn1 : P1.y) : (e ? P1.y : P1.x);
+                };
+                derived_cell<TopoRectT<false>, true>(g, A.alpha, U, V, P, X, Y, m, e ? k1 : k0, p[e], wv[e], d[e]);
+            }
+            if (wr) {   // (an odd ny's last pair: column ny is row padding, left untouched)
+                const ptrdiff_t o = (ptrdiff_t)m * ld + c0;
+                if (v1) {
+                    if (A.op) st_stream(A.op + o, make_double2(p[0], p[1]), false);
+                    if (A.ow) st_stream(A.ow + o, make_double2(wv[0], wv[1]), false);
+                    if (A.od) st_stream(A.od + o, make_double2(d[0], d[1]), false);
+                } else {
+                    if (A.op) A.op[o] = p[0];
+                    if (A.ow) A.ow[o] = wv[0];
+                    if (A.od) A.od[o] = d[0];
+                }
+            }
+            if (o0) derived_acc(xr[0], ya[0], xr[5], ya[5], U1.x, V1.x, p[0], wv[0], d[0], as, am, ap);
+            if (o1) derived_acc(xr[0], yb[0], xr[5], yb[5], U1.y, V1.y, p[1], wv[1], d[1], as, am, ap);
+        };
+        const int r0 = ib - 1, r1 = ie;
+#pragma unroll
+        for (int q = 0; q < DV_SD; q++) load(r0 + q, QU[q], QV[q], QP[q]);
+        for (int r = r0; r <= r1; r += DV_SD) {
+#pragma unroll
+            for (int q = 0; q < DV_SD; q++) {
+                if (r + q <= r1) step(QU[q], QV[q], QP[q], r + q);
+                load(r + q + DV_SD, QU[q], QV[q], QP[q]);
+            }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) as[k] += __shfl_xor(as[k], off, 64);
+#pragma unroll
+        for (int k = 0; k < 4; k++) am[k] = fmin(am[k], __shfl_xor(am[k], off, 64));
+#pragma unroll
+        for (int k = 0; k < 2; k++) ap[k] = fmin(ap[k], __shfl_xor(ap[k], off, 64));
+    }
+    if (lane == 0 && w < nstr) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) A.ps[3 * w + k] = as[k];
+#pragma unroll
+        for (int k = 0; k < 4; k++) A.pa[4 * w + k] = am[k];
+#pragma unroll
+        for (int k = 0; k < 2; k++) A.pb[2 * w + k] = ap[k];
+    }
+}
+
+// ---- the stream function at the cell vertices: psi(i, j) = the volume flux through the vertical line from the box's
+// bottom to vertex (i, j).  The flux of the x-face between cells (i - 1, j) and (i, j): the interior face value if
+// both are in the domain, the one cell's boundary-face value if one is, 0 if neither (psi is constant across holes
+// and outside regions)
+template <class T>
+__device__ __forceinline__ double psi_flux(const Geo& g, const Coef& c, const double* __restrict__ u, int i, int j) {
+    const bool a = i > 0 && T(g, i - 1, j).cell(), b = i < g.nx && T(g, i, j).cell();
+    double f = 0.0;
+    if (a && b) {
+        f = dv_face(u[(ptrdiff_t)i * g.ld + j], u[(ptrdiff_t)(i - 1) * g.ld + j], c.fwx[i]);
+    } else if (b) {
+        const double uc = u[(ptrdiff_t)i * g.ld + j];
+        f = dv_wall(uc, T(g, i, j).gv(0, 0, 0, uc, 0));
+    } else if (a) {
+        const double uc = u[(ptrdiff_t)(i - 1) * g.ld + j];
+        f = dv_wall(uc, T(g, i - 1, j).gv(0, 0, 1, uc, 0));
+    }
+    return dv_mul(f, c.hy[j]);
+}
+__device__ __forceinline__ double wave_scan_incl(double x, int lane) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const double y = __shfl_up(x, off, 64);
+        if (lane >= off) x += y;
+    }
+    return x;
+}
+// base[i] = psi(i, 0): the prefix sum over i of -v_S(i, 0) hx[i] (the S boundary-face value of cell (i, 0), 0 if
+// that cell is outside), base[0] = 0.  One workgroup
+template <class T>
+__global__ __launch_bounds__(1024) void k_psi_base(Geo g, Coef c, const double* __restrict__ v, double* __restrict__ base) {
+    __shared__ double wt[16];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    double carry = 0.0;
+    if (tid == 0) base[0] = 0.0;
+    for (int ib = 0; ib < g.nx; ib += 1024) {
+        const int i = ib + tid;
+        double x = 0.0;
+        if (i < g.nx) {
+            const T t(g, i, 0);
+            if (t.cell()) {
+                const double vc = v[(ptrdiff_t)i * g.ld];
+                x = -dv_mul(dv_wall(vc, t.gv(0, 0, 2, vc, 1)), c.hx[i]);
+            }
+        }
+        x = wave_scan_incl(x, lane);
+        if (lane == 63) wt[wv] = x;
+        __syncthreads();
+        double off = carry, tot = 0.0;
+        for (int q = 0; q < 16; q++) {
+            if (q < wv) off += wt[q];
+            tot += wt[q];
+        }
+        if (i < g.nx) base[i + 1] = off + x;
+        carry += tot;
+        __syncthreads();
+    }
+}
+// one wave per vertex row i = 0 .. nx: j in chunks of 64, the faces' fluxes, a wave inclusive scan on a running
+// base, coalesced stores into the vertex plane (rows of ldv doubles); (min, -max) of the row at part + 2 i
+template <class T>
+__global__ __launch_bounds__(256) void k_psi_scan(Geo g, Coef c, const double* __restrict__ u,
+                                                  const double* __restrict__ base, double* __restrict__ psi, int ldv,
+                                                  double* __restrict__ part) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    if (i > g.nx) return;
+    double run = base[i];
+    double* row = psi + (ptrdiff_t)i * ldv;
+    if (lane == 0) row[0] = run;
+    double mn = dv_min(INFINITY, run), mx = dv_min(INFINITY, -run);
+    for (int jb = 0; jb < g.ny; jb += 64) {
+        const int j = jb + lane;
+        const double f = j < g.ny ? psi_flux<T>(g, c, u, i, j) : 0.0;
+        const double val = run + wave_scan_incl(f, lane);
+        if (j < g.ny) {
+            row[j + 1] = val;
+            mn = dv_min(mn, val);
+            mx = dv_min(mx, -val);
+        }
+        run = __shfl(val, 63, 64);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        mn = fmin(mn, __shfl_xor(mn, off, 64));
+        mx = fmin(mx, __shfl_xor(mx, off, 64));
+    }
+    if (lane == 0) {
+        part[2 * i] = mn;
+        part[2 * i + 1] = mx;
+    }
+}
+
 // ------------------------------------------------ K2 / K4: two sweeps per HBM pass
 // Temporal blocking of k_sweep<RB>: the row pipeline carries four stages -- red of
 // sweep 1 at row r-1, black 1 at r-2, red 2 at r-3, black 2 at r-4 -- so one read of
@@ -4643,6 +5030,18 @@ __global__ __launch_bounds__(1024) void k_reduce_step(const double* __restrict__
     else reduce_min_body(pm, ns, 4, outm, reinterpret_cast<double (*)[4]>(sh));
 }
 
+// the derived fields' partials in one launch of four workgroups: the n cell-pass partials -- 3 sums -> out[0..3),
+// 4 minima -> out[3..7), 2 minima -> out[7..9) -- and psi's np (min, -max) rows -> out[9..11) (np = 0: +inf)
+__global__ __launch_bounds__(1024) void k_derived_reduce(const double* __restrict__ ps, const double* __restrict__ pa,
+                                                         const double* __restrict__ pb, int n,
+                                                         const double* __restrict__ pp, int np, double* __restrict__ out) {
+    __shared__ double sh[1024];
+    if (blockIdx.x == 0) reduce_sum_body(ps, n, 3, out, sh);
+    else if (blockIdx.x == 1) reduce_min_body(pa, n, 4, out + 3, reinterpret_cast<double (*)[4]>(sh));
+    else if (blockIdx.x == 2) reduce_min_body(pb, n, 2, out + 7, reinterpret_cast<double (*)[4]>(sh));
+    else reduce_min_body(pp, np, 2, out + 9, reinterpret_cast<double (*)[4]>(sh));
+}
+
 // one rank: k_reduce_sum of the (sum, sum^2) partials and k_finish_mean in one launch (no
 // all-reduce between them; the same arithmetic in the same order)
 __global__ __launch_bounds__(1024) void k_reduce_sum_mean(const double* __restrict__ p, int n,
@@ -5530,6 +5929,53 @@ int launch_minmax(const Geo& g, const double* f, double* part, hipStream_t st) {
     const dim3 cg = cell_grid(g, rows);
     NS_LAUNCH(k_minmax, cg, dim3(64, 4), 0, st, g, f, part, rows);
     return (int)(cg.x * cg.y);
+}
+
+// the derived fields' cell pass streams here (one rank's rectangle without an edge profile; the rest is thread per cell)
+static bool derived_streams(const Knobs& kn, const Geo& g) { return !kn.cell_grid && !g.fc && !geo_profiled(g); }
+int derived_partials(const Geo& g) {
+    const int rows = cell_rows(g);
+    const dim3 cg = cell_grid(g, rows);
+    const int strips = ((g.nxl + 3) / 4) * ((g.ny + SW - 1) / SW);   // strip rows >= 4
+    return std::max((int)(cg.x * cg.y), strips);
+}
+int launch_derived(const Knobs& kn, const Geo& g, const Coef& c, double alpha, const double* u, const double* v,
+                   const double* phi, double* op, double* ow, double* od, double* part, hipStream_t st) {
+    if (g_phase != 0 || g.nxl != g.nx) return -1;   // (one rank: ns_derive refuses the rest)
+    const size_t np = (size_t)derived_partials(g);
+    double *ps = part, *pa = part + 3 * np, *pb = part + 7 * np;
+    if (derived_streams(kn, g)) {
+        DerivedStreamArgs A{};
+        A.g = g; A.c = c; A.alpha = alpha; A.u = u; A.v = v; A.phi = phi; A.op = op; A.ow = ow; A.od = od;
+        A.ps = ps; A.pa = pa; A.pb = pb;
+        A.nsj = (g.ny + SW - 1) / SW;
+        const int L = strip_rows(g.nxl, A.nsj, resident_waves(kn, (const void*)k_derived_s), 4);
+        const int nstr = A.nsj * plan_rows(g.nxl, L, 1, &A.P);   // window rows ib - 1 .. ie
+        NS_LAUNCH(k_derived_s, dim3((nstr + 3) / 4), dim3(256), 0, st, A);
+        return nstr;
+    }
+    const int rows = cell_rows(g);
+    const dim3 cg = cell_grid(g, rows);
+    if (g.fc) NS_LAUNCH(k_derived_grid<TopoMask>, cg, dim3(64, 4), 0, st, g, c, alpha, u, v, phi, op, ow, od, ps, pa, pb, rows);
+    else NS_LAUNCH(k_derived_grid<TopoRect>, cg, dim3(64, 4), 0, st, g, c, alpha, u, v, phi, op, ow, od, ps, pa, pb, rows);
+    return (int)(cg.x * cg.y);
+}
+int launch_psi(const Geo& g, const Coef& c, const double* u, const double* v, double* base, double* psi, int ldv,
+               double* part, hipStream_t st) {
+    if (g.nxl != g.nx) return -1;
+    const dim3 sg((g.nx + 1 + 3) / 4);
+    if (g.fc) {
+        NS_LAUNCH(k_psi_base<TopoMask>, dim3(1), dim3(1024), 0, st, g, c, v, base);
+        NS_LAUNCH(k_psi_scan<TopoMask>, sg, dim3(256), 0, st, g, c, u, base, psi, ldv, part);
+    } else {
+        NS_LAUNCH(k_psi_base<TopoRect>, dim3(1), dim3(1024), 0, st, g, c, v, base);
+        NS_LAUNCH(k_psi_scan<TopoRect>, sg, dim3(256), 0, st, g, c, u, base, psi, ldv, part);
+    }
+    return g.nx + 1;
+}
+void launch_derived_reduce(const double* part, int n, int ncap, const double* pp, int np, double* out, hipStream_t st) {
+    NS_LAUNCH(k_derived_reduce, dim3(4), dim3(1024), 0, st, part, part + 3 * (size_t)ncap, part + 7 * (size_t)ncap, n, pp,
+              np, out);
 }
 
 template <int K>

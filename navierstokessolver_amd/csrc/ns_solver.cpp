@@ -393,6 +393,15 @@ struct ns_solver {
         double bx = 0.0, by = 0.0, tref = 0.0;
         bool buoyant() const { return on && (bx != 0.0 || by != 0.0); }
     } sc;
+    // derived fields (ns_derive; DESIGN.md 4 "Derived fields"): nothing below exists before the first call.  The
+    // planes (nxl x ld, no ghost rows) and psi's vertex plane ((nx + 1) rows of ldv) each on first request; partials,
+    // result slots and their pinned mirror of its own, so that no slot a later step reads is touched
+    struct Derived {
+        enum { NSLOT = 16 };   // 3 sums, 4 + 2 minima, psi's (min, -max)
+        double *p = nullptr, *w = nullptr, *d = nullptr, *psi = nullptr, *base = nullptr;
+        double *part = nullptr, *ppart = nullptr, *scal = nullptr, *hs = nullptr;
+        int ncap = 0, ldv = 0;
+    } dv;
 };
 
 namespace {
@@ -4133,6 +4142,9 @@ void ns_destroy(ns_solver* s) {
     (void)hipSetDevice(s->device);
     if (s->st) (void)hipStreamSynchronize(s->st);
     scalar_free(s);
+    for (double* q : {s->dv.p, s->dv.w, s->dv.d, s->dv.psi, s->dv.base, s->dv.part, s->dv.ppart, s->dv.scal})
+        if (q) (void)hipFree(q);
+    if (s->dv.hs) (void)hipHostFree(s->dv.hs);
     if (s->comm) (void)ncclCommDestroy(s->comm);
     if (s->mev) (void)hipEventDestroy(s->mev);
     if (s->mm_host) (void)hipHostFree(s->mm_host);
@@ -4392,6 +4404,77 @@ int ns_set_array(ns_solver* s, int which, const double* host) {
         for (int& h : s->mg_hist) h = -1;   // an injected state: no cycle-count history
     if (which == NS_ARR_RU || which == NS_ARR_RV) CHK(helm_bnorm(s));
     HIPCHK(hipStreamSynchronize(s->st));
+    return 0;
+}
+
+// ---------------- derived fields ("Derived fields"): P, vorticity, divergence, psi and the integrals of
+// the current u, v, phi.  One cell pass (24 B/cell in, only the planes asked for out) + psi's two launches + one
+// reduction, all on the solver's stream with buffers of its own
+int ns_derive(ns_solver* s, const ns_derived* out, ns_derived_stats* st) {
+    if (!s) { set_err("null solver"); return NS_EINVAL; }
+    if (!out && !st) { set_err("ns_derive: out and st are both NULL"); return NS_EINVAL; }
+    if (s->nranks > 1) { set_err("ns_derive: nranks > 1 is not supported"); return NS_EINVAL; }
+    CHK(materialize(s));
+    HIPCHK(hipSetDevice(s->device));
+    nsg::set_compute_cus(s->compute_cus);
+    using D = ns_solver::Derived;
+    auto& q = s->dv;
+    const nsg::Geo& g = s->g;
+    const ns_derived none{nullptr, nullptr, nullptr, nullptr};
+    const ns_derived& o = out ? *out : none;
+    const size_t pl = (size_t)g.nxl * g.ld * sizeof(double);
+    if (!q.part) {
+        q.ncap = nsg::derived_partials(g);
+        CHK(dev_alloc(s, &q.part, (size_t)q.ncap * 9 * sizeof(double), false, "derived partials"));
+        CHK(dev_alloc(s, &q.scal, D::NSLOT * sizeof(double), true, "derived slots"));
+        if (hipHostMalloc(&q.hs, D::NSLOT * sizeof(double), hipHostMallocDefault) != hipSuccess) { set_err("hipHostMalloc failed"); return NS_ENOMEM; }
+    }
+    if (o.p && !q.p) CHK(dev_alloc(s, &q.p, pl, true, "pressure plane"));
+    if (o.vort && !q.w) CHK(dev_alloc(s, &q.w, pl, true, "vorticity plane"));
+    if (o.div && !q.d) CHK(dev_alloc(s, &q.d, pl, true, "divergence plane"));
+    if (o.psi && !q.psi) {
+        q.ldv = (g.ny + 1 + 15) & ~15;
+        CHK(dev_alloc(s, &q.psi, (size_t)(g.nx + 1) * q.ldv * sizeof(double), true, "stream-function plane"));
+        CHK(dev_alloc(s, &q.base, (size_t)(g.nx + 1) * sizeof(double), false, "stream-function base"));
+        CHK(dev_alloc(s, &q.ppart, (size_t)(g.nx + 1) * 2 * sizeof(double), false, "stream-function partials"));
+    }
+    Timing::Scope iv;
+    TCHK(s->tm.open(iv, nsg::T_DERIVED, s->timing));
+    const int nb = nsg::launch_derived(s->k, g, s->c, s->dt / (2 * s->re), s->arr[NS_ARR_U], s->arr[NS_ARR_V],
+                                       s->arr[NS_ARR_PHI], o.p ? q.p : nullptr, o.vort ? q.w : nullptr,
+                                       o.div ? q.d : nullptr, q.part, s->st);
+    if (nb < 0) { set_err("ns_derive: the cell pass's launch was refused"); return NS_EHIP; }
+    TCHK(iv.close());
+    int np = 0;
+    if (o.psi) {
+        np = nsg::launch_psi(g, s->c, s->arr[NS_ARR_U], s->arr[NS_ARR_V], q.base, q.psi, q.ldv, q.ppart, s->st);
+        if (np < 0) { set_err("ns_derive: the stream function's launch was refused"); return NS_EHIP; }
+    }
+    nsg::launch_derived_reduce(q.part, nb, q.ncap, q.ppart, np, q.scal, s->st);
+    HIPCHK(hipMemcpyAsync(q.hs, q.scal, D::NSLOT * sizeof(double), hipMemcpyDeviceToHost, s->st));
+    const size_t wb = (size_t)g.ny * 8, ldb = (size_t)g.ld * 8;
+    if (o.p) HIPCHK(hipMemcpy2DAsync(o.p, wb, q.p, ldb, wb, g.nxl, hipMemcpyDeviceToHost, s->st));
+    if (o.vort) HIPCHK(hipMemcpy2DAsync(o.vort, wb, q.w, ldb, wb, g.nxl, hipMemcpyDeviceToHost, s->st));
+    if (o.div) HIPCHK(hipMemcpy2DAsync(o.div, wb, q.d, ldb, wb, g.nxl, hipMemcpyDeviceToHost, s->st));
+    if (o.psi)
+        HIPCHK(hipMemcpy2DAsync(o.psi, (size_t)(g.ny + 1) * 8, q.psi, (size_t)q.ldv * 8, (size_t)(g.ny + 1) * 8, g.nx + 1,
+                                hipMemcpyDeviceToHost, s->st));
+    HIPCHK(hipStreamSynchronize(s->st));
+    ns_derived_stats r{};
+    TCHK(s->tm.drain(nsg::tbit(nsg::T_DERIVED), nullptr, nullptr, &r));
+    const double* h = q.hs;
+    r.ke = 0.5 * h[0];
+    r.enstrophy = 0.5 * h[1];
+    r.div_l2 = std::sqrt(h[2]);
+    r.div_max = -h[3];
+    r.cfl = s->dt * -h[4];
+    r.vort_min = h[5];
+    r.vort_max = -h[6];
+    r.p_min = h[7];
+    r.p_max = -h[8];
+    r.psi_min = o.psi ? h[9] : NAN;
+    r.psi_max = o.psi ? -h[10] : NAN;
+    if (st) *st = r;
     return 0;
 }
 

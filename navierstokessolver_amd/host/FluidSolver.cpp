@@ -23,6 +23,7 @@ struct Options {
     double rtol = 1e-8;
     int device = 0;
     bool do_export = true;
+    bool derived = false;   // -derived: Derived_<iter>.csv beside every export, one summary line after the last step
 };
 Options g_opt;
 
@@ -46,6 +47,8 @@ PetscErrorCode PetscInitialize(int* argc, char*** argv, const char*, const char*
         } else if (!std::strcmp(a, "-no_export")) {
             g_opt.do_export = false;
             ns_export_files = false;   // CellCenters.csv too (Grid.cpp)
+        } else if (!std::strcmp(a, "-derived")) {
+            g_opt.derived = true;
         } else {
             keep.push_back((*argv)[k]);  // positional arguments (grid file, sim file) stay
         }
@@ -244,6 +247,22 @@ void write_flow_csv(int iter, Grid& g, double dt, double re, const vector<double
         }
 }
 
+// -derived: the device's vorticity, divergence and pressure (ns_derive) at the cell centres of FlowData_<iter>.csv,
+// in its order
+void write_derived_csv(int iter, Grid& g, const vector<double>& w, const vector<double>& d, const vector<double>& p) {
+    const int nx = g.nxCells(), ny = g.nyCells();
+    char name[64];
+    std::snprintf(name, sizeof name, "Derived_%d.csv", iter);
+    ofstream fs{name};
+    fs << "Point_X,Point_Y,Vorticity,Divergence,Pr\n";
+    for (int i = 0; i < nx; i++)
+        for (int j = 0; j < ny; j++) {
+            if (!g.inDomain(i, j)) continue;
+            const size_t c = (size_t)i * ny + j;
+            fs << g.centerX(i) << "," << g.centerY(j) << "," << w[c] << "," << d[c] << "," << p[c] << endl;
+        }
+}
+
 }  // namespace
 
 void FluidSolver::Solve() {
@@ -252,6 +271,7 @@ void FluidSolver::Solve() {
     cout << "Initiating Solver..\n";
     const size_t n = (size_t)m.nx * m.ny;
     vector<double> u, v, phi;   // host copies for the export only (allocated on the first one)
+    vector<double> dw, dd, dp;  // -derived: the device's vorticity, divergence, pressure
     int iter = 1;
     do {
         ns_stats st{};
@@ -268,9 +288,21 @@ void FluidSolver::Solve() {
             if (ns_get_array(m.gpu, NS_ARR_U, u.data()) == 0 && ns_get_array(m.gpu, NS_ARR_V, v.data()) == 0 &&
                 ns_get_array(m.gpu, NS_ARR_PHI, phi.data()) == 0)
                 write_flow_csv(iter, *grid, m.p.dt, m.p.re, u, v, phi);
+            if (g_opt.derived) {
+                if (dw.empty()) dw.resize(n), dd.resize(n), dp.resize(n);
+                const ns_derived out{dp.data(), dw.data(), dd.data(), nullptr};
+                if (ns_derive(m.gpu, &out, nullptr) == 0) write_derived_csv(iter, *grid, dw, dd, dp);
+                else cout << "Derived fields failed: " << ns_last_error() << "\n";
+            }
         }
         iter++;
     } while (m.p.dt * iter <= m.p.finalTime);
+    if (g_opt.derived) {
+        ns_derived_stats ds{};
+        if (ns_derive(m.gpu, nullptr, &ds) == 0)
+            printf("derived: ke %.9e enstrophy %.9e div_max %.9e cfl %.9e\n", ds.ke, ds.enstrophy, ds.div_max, ds.cfl);
+        else cout << "Derived fields failed: " << ns_last_error() << "\n";
+    }
     fflush(stdout);
     cout << "Solution Complete!\n";
 }

@@ -189,6 +189,20 @@ class GpuSolver:
         n = 0 if e is None else (self.grid.ny if e.nx != 0 else self.grid.nx)
         L.check(L.lib().ns_edge_profile(self._h, int(edge), None, n))
 
+    # ---- derived fields (ns_derive: one rank)
+    def derived(self, p: bool = True, vort: bool = True, div: bool = True, psi: bool = True) -> dict:
+        """Pressure, vorticity and divergence as (nx, ny) planes (0 outside a polygon), the stream function at the
+        (nx + 1, ny + 1) cell vertices -- each only if asked for -- and ns_derived_stats under its field names (ke,
+        enstrophy, div_l2, div_max, cfl, vort_min / max, p_min / max, psi_min / max: NaN without psi).  Between
+        steps; all four False is a stats-only pass."""
+        nx, ny = self.shape
+        want = {"p": p, "vort": vort, "div": div, "psi": psi}
+        arrs = {k: np.empty((nx + 1, ny + 1) if k == "psi" else (nx, ny), dtype=np.float64) for k, w in want.items() if w}
+        out = L.NsDerived(*[_dptr(arrs[k]) if k in arrs else None for k in ("p", "vort", "div", "psi")])
+        st = L.NsDerivedStats()
+        L.check(L.lib().ns_derive(self._h, ctypes.byref(out), ctypes.byref(st)))
+        return {**arrs, **st.as_dict()}
+
     # ---- passive scalar (ns_scalar_*: one rank's rectangle)
     def enable_scalar(self, pe: float, bc) -> None:
         """A scalar T carried by the step, Peclet number pe.  bc: one ("dirichlet", value) or ("zerograd",)
