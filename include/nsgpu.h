@@ -362,6 +362,52 @@ typedef struct ns_derived_stats {
 } ns_derived_stats;
 int  ns_derive(ns_solver* s, const ns_derived* out, ns_derived_stats* st);   /* either may be NULL, not both */
 
+/* ---- Lagrangian tracer particles carried by the time step ----
+ * Massless particles that follow the flow on the device ("Tracers"; the normative statement is
+ * tests/tracer_ref.py).  Positions are physical coordinates relative to the bounding box's lower-left corner
+ * (ns_grid_desc carries no origin: a caller whose grid starts elsewhere subtracts it).  Once enabled and holding
+ * particles, every ns_step / ns_step_async advances them by the solver's dt in u^n, v^n, right after K1 -- no host
+ * sync is added to the step; a solver that never enables them runs exactly the launches it ran before.
+ *   sampling: bilinear between cell centres; where a neighbour is not in the domain, the boundary value 0.5 (q + ghost)
+ *             at the boundary face (the edge's velocity ghost, its ns_edge_profile entry where one is set).  Continuous
+ *             across interior faces, exact for a field linear in x and y away from boundary faces, discontinuous only
+ *             at re-entrant corners.
+ *   advance:  AB2, x += dt (1.5 w^n - 0.5 w^{n-1}), an Euler step on a particle's first; age += dt.
+ *   fate:     a particle whose new position is in no domain cell does not move: it is EXITED if it left through a
+ *             NEUMANN or INLET_UNI face, STUCK at a wall, at a jump past a corner, or on a non-finite value.  A particle
+ *             that is not LIVE keeps its position, sample and age and is never touched again.  Keeping the CFL number
+ *             below 1 is the caller's business: a jump over a thin divider into another part of the domain lands LIVE.
+ * Particle indices are stable (no compaction): a caller follows individuals, and re-injects for streaklines by
+ * adding between steps.
+ * ns_tracers_enable: once per solver; its planes (44 B per particle of capacity) are not counted by ns_device_bytes.
+ * ns_tracers_add:    appends at [n, n + count), all or nothing; new particles are fresh with age 0.
+ * ns_tracers_get:    particles [first, first + n); any pointer may be NULL; synchronises.
+ * ns_tracers_sample: w at the current positions, n doubles each (a particle that is not LIVE: the sample it froze with).
+ * ns_tracers_advance: `steps` advances of dt in the current u, v held fixed (tests; pathlines of a steady field).
+ * ns_tracers_reset:  n = 0.
+ * ns_tracers_last:   the counts after the latest advance (of a step, or of ns_tracers_advance: seeds added since are
+ *                    in n, not yet in live) and that advance's kernel time, handed out once; synchronises.
+ * ns_tracers_sample / _advance settle a deferred correction (ns_step_async) first, as ns_get_array does.
+ * NS_EINVAL (the message names the cause): a null solver, not enabled, enabled twice, capacity <= 0, nranks > 1
+ * (particles would migrate between slabs), an add past the capacity, a seed that is not finite or not in a domain cell
+ * (the message gives its index), dt not finite, steps < 0, a get range outside [0, n).  Additive to ABI 9. */
+#define NS_TRACER_LIVE   0
+#define NS_TRACER_EXITED 1
+#define NS_TRACER_STUCK  2
+typedef struct ns_tracer_stats {
+    int64_t n, live, exited, stuck;
+    double  age_max;             /* of the live ones, 0 if none */
+    double  t_kernel_ms;         /* the latest advance's particle kernels (timing == 1) */
+    int32_t n_kernels;
+} ns_tracer_stats;
+int  ns_tracers_enable(ns_solver* s, int64_t capacity);
+int  ns_tracers_add(ns_solver* s, const double* x, const double* y, int64_t n);
+int  ns_tracers_get(ns_solver* s, int64_t first, int64_t n, double* x, double* y, double* age, int32_t* state);
+int  ns_tracers_sample(ns_solver* s, double* u, double* v);
+int  ns_tracers_advance(ns_solver* s, double dt, int32_t steps);
+int  ns_tracers_reset(ns_solver* s);
+int  ns_tracers_last(ns_solver* s, ns_tracer_stats* out);
+
 /* ---- host-side helpers (no GPU needed) ---- */
 /* the face averages of the parabola 6 s (1 - s) * mean over the faces k0 <= k < k1 of spacings h[0..n) (s runs 0..1
  * from face k0's lower end to face k1-1's upper end), 0 elsewhere: the average over [sa, sb] is

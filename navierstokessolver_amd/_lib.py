@@ -120,6 +120,18 @@ class NsDerivedStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+NS_TRACER_LIVE, NS_TRACER_EXITED, NS_TRACER_STUCK = 0, 1, 2
+
+
+class NsTracerStats(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_int64), ("live", ctypes.c_int64), ("exited", ctypes.c_int64),
+                ("stuck", ctypes.c_int64), ("age_max", ctypes.c_double), ("t_kernel_ms", ctypes.c_double),
+                ("n_kernels", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _P = ctypes.c_void_p
 _D = ctypes.POINTER(ctypes.c_double)
 SIGNATURES = {
@@ -148,6 +160,13 @@ SIGNATURES = {
     "ns_scalar_buoyancy": (ctypes.c_int, [_P, ctypes.POINTER(NsBuoyancyDesc)]),
     "ns_edge_profile": (ctypes.c_int, [_P, ctypes.c_int32, _D, ctypes.c_int32]),
     "ns_derive": (ctypes.c_int, [_P, ctypes.POINTER(NsDerived), ctypes.POINTER(NsDerivedStats)]),
+    "ns_tracers_enable": (ctypes.c_int, [_P, ctypes.c_int64]),
+    "ns_tracers_add": (ctypes.c_int, [_P, _D, _D, ctypes.c_int64]),
+    "ns_tracers_get": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int64, _D, _D, _D, ctypes.POINTER(ctypes.c_int32)]),
+    "ns_tracers_sample": (ctypes.c_int, [_P, _D, _D]),
+    "ns_tracers_advance": (ctypes.c_int, [_P, ctypes.c_double, ctypes.c_int32]),
+    "ns_tracers_reset": (ctypes.c_int, [_P]),
+    "ns_tracers_last": (ctypes.c_int, [_P, ctypes.POINTER(NsTracerStats)]),
     "ns_parabolic_profile": (ctypes.c_int, [_D, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, _D]),
     "ns_slab_range": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                      ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),

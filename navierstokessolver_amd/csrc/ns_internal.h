@@ -151,6 +151,28 @@ int launch_psi(const Geo& g, const Coef& c, const double* u, const double* v, do
 // the n cell-pass partials (blocks of capacity ncap, launch_derived's layout) and psi's np rows -> out[0..11): the 3
 // sums, the 4 + 2 minima, psi's (min, -max) (np = 0: +inf)
 void launch_derived_reduce(const double* part, int n, int ncap, const double* pp, int np, double* out, hipStream_t st);
+// tracer particles (ns_tracers_*; DESIGN.md 4, "Tracers"): SoA planes of n particles -- position, the previous
+// step's sample, age (doubles) and the state word (bits 0..1 NS_TRACER_*, bit 2 fresh) -- advanced in the fields u, v
+// of geometry g (one rank).  xf / yf: the cell faces from the box's lower-left corner (nx + 1 / ny + 1 doubles);
+// rhx / rhy: cells per unit length on a uniform axis (the cell search multiplies and fixes up against the faces), 0:
+// binary search.  exitm: bit e set -- a particle leaving through edge e (a rectangle: side e) has EXITED, else it is
+// STUCK
+struct TracerArgs {
+    Geo g;
+    const double *xf, *yf;
+    double rhx, rhy;
+    const double *u, *v;
+    double *x, *y, *wu, *wv, *age;
+    int32_t* st;
+    double *su, *sv;      // mode 0's output
+    double* part;         // mode 2's partials: 4 per block (3 sums, then the minima after all blocks' sums)
+    int64_t n;
+    double dt;
+    unsigned exitm;
+};
+// mode 0: sample only, 1: advance, 2: advance and count; returns the block count (tracer_blocks(n)), -1 if refused
+int tracer_blocks(int64_t n);
+int launch_tracer(const TracerArgs& A, int mode, hipStream_t st);
 // K2: fused red-black SOR sweep of (I - a L_V) on u and v, (u,v) -> (uo,vo);
 //     residual^2 partials of the input if part != null: u at part[0..n), v at part[n..2n), n returned
 int launch_helm_sweep(const Knobs& kn, const Geo& g, const Coef& c, double alpha, double omega, const double* u, const double* v,

@@ -5978,6 +5978,192 @@ void launch_derived_reduce(const double* part, int n, int ncap, const double* pp
               np, out);
 }
 
+// ---------------------------------------------------------------- tracer particles (ns_tracers_*; DESIGN.md 4,
+// "Tracers"; the normative statement is tests/tracer_ref.py).  One thread per particle, grid-stride: locate the cell,
+// sample (u, v) bilinearly between cell centres -- the boundary value at the boundary face where a neighbour is not
+// in the domain --, one AB2 step (Euler on a particle's first), locate again and settle the fate.
+// The expressions the statement fixes, contraction off: TopoRect and TopoMask then agree bit for bit
+__device__ __forceinline__ double tr_lerp(double q, double w, double qn) {
+#pragma clang fp contract(off)
+    return q + w * (qn - q);
+}
+__device__ __forceinline__ double tr_weight(double x, double xc, double xn) {
+#pragma clang fp contract(off)
+    return (x - xc) / (xn - xc);
+}
+__device__ __forceinline__ double tr_wall(double q, double gh) {
+#pragma clang fp contract(off)
+    return 0.5 * (q + gh);
+}
+__device__ __forceinline__ double tr_mid(const double* __restrict__ f, int i) {
+#pragma clang fp contract(off)
+    return 0.5 * (f[i] + f[i + 1]);
+}
+__device__ __forceinline__ double tr_euler(double x, double dt, double w) {
+#pragma clang fp contract(off)
+    return x + dt * w;
+}
+__device__ __forceinline__ double tr_ab2(double x, double dt, double w, double wp) {
+#pragma clang fp contract(off)
+    return x + dt * (1.5 * w - 0.5 * wp);
+}
+// the cell of x along an axis of n cells with faces f[0..n]: f[i] <= x < f[i + 1]; -1 below the box, n at or above
+// its end, -2 for a NaN.  rh > 0 (uniform spacing, n / f[n]): multiply, then fix up against f; else binary search --
+// the same cell either way.  Every index the result is used with lies in [0, n)
+__device__ __forceinline__ int tr_locate(const double* __restrict__ f, int n, double rh, double x) {
+    if (!(x >= 0.0)) return x < 0.0 ? -1 : -2;
+    if (!(x < f[n])) return n;
+    if (rh > 0.0) {
+        const double t = x * rh;
+        int i = t < (double)(n - 1) ? (int)t : n - 1;
+        while (i > 0 && x < f[i]) i--;
+        while (i < n - 1 && x >= f[i + 1]) i++;
+        return i;
+    }
+    int lo = 0, hi = n;   // f[lo] <= x < f[hi]
+    while (hi - lo > 1) {
+        const int m = (lo + hi) >> 1;
+        if (x >= f[m]) lo = m;
+        else hi = m;
+    }
+    return lo;
+}
+// the edge on face k of the topology's cell: the side itself on a rectangle, the polygon's edge index on a mask
+// (the bit of TracerArgs::exitm)
+__device__ __forceinline__ int tr_edge(const TopoRect&, int k) { return k; }
+__device__ __forceinline__ int tr_edge(const TopoMask& t, int k) { return fc_edge(t.code, k); }
+
+// component d (plane q) at (x, y), a point of the domain cell (i, j) (t: its topology): row by row -- R(j') along x
+// with row j''s own x-node (the neighbour's centre, or cell (i, j')'s boundary face with 0.5 (q + ghost)), then along
+// y between R(j) and R(j + sy) or the y-face's value of R(j).  Loads only cells `in` says are in the domain
+template <class T>
+__device__ __forceinline__ double tr_sample(const TracerArgs& A, const T& t, const double* __restrict__ q, int d,
+                                            double x, double y, int i, int j, double xc, double yc) {
+    const int ld = A.g.ld;
+    const ptrdiff_t o = (ptrdiff_t)i * ld + j;
+    const int sx = x >= xc ? 1 : -1, sy = y >= yc ? 1 : -1;
+    const int kx = sx > 0 ? 1 : 0, ky = sy > 0 ? 3 : 2;
+    const double xface = A.xf[sx > 0 ? i + 1 : i];
+    auto row = [&](int dj, bool has) {
+        const double qc = q[o + dj];
+        double xn, qn;
+        if (has) {
+            xn = tr_mid(A.xf, i + sx);
+            qn = q[o + (ptrdiff_t)sx * ld + dj];
+        } else {
+            xn = xface;
+            qn = tr_wall(qc, t.gv(0, dj, kx, qc, d));
+        }
+        return tr_lerp(qc, tr_weight(x, xc, xn), qn);
+    };
+    const double a = row(0, t.in(sx, 0));
+    double yn, b;
+    if (t.in(0, sy)) {
+        b = row(sy, t.in(sx, sy));
+        yn = tr_mid(A.yf, j + sy);
+    } else {
+        yn = A.yf[sy > 0 ? j + 1 : j];
+        b = tr_wall(a, t.gv(0, 0, ky, a, d));
+    }
+    return tr_lerp(a, tr_weight(y, yc, yn), b);
+}
+
+// MODE 0: sample only (su, sv <- w at the current positions; a particle that is not live reports the sample it froze
+// with), 1: advance, 2: advance and count (per block 3 sums -- live, exited, stuck -- at part, then -max age of the
+// live ones at part + 3 nb).  State word: bits 0..1 NS_TRACER_*, bit 2 fresh (no w^{n-1} yet: an Euler step).
+// A lane that is not live reads its state word and nothing else of the planes (MODE 0 apart)
+template <class T, int MODE>
+__global__ __launch_bounds__(256) void k_tracer(TracerArgs A) {
+    const Geo& g = A.g;
+    double cnt[3] = {0.0, 0.0, 0.0}, am[1] = {INFINITY};
+    for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < A.n; p += (int64_t)gridDim.x * 256) {
+        const int sf = A.st[p];
+        int state = sf & 3;
+        double age = 0.0;
+        if (state == 0) {
+            const double x = A.x[p], y = A.y[p];
+            const int i = tr_locate(A.xf, g.nx, A.rhx, x), j = tr_locate(A.yf, g.ny, A.rhy, y);
+            // (a live particle sits in a domain cell; anything else -- a corrupted plane -- is stuck, not an index)
+            bool ok = i >= 0 && i < g.nx && j >= 0 && j < g.ny;
+            int ns = 2;
+            if (ok) {
+                const T t(g, i, j);
+                ok = t.cell();
+                if (ok) {
+                    const double xc = tr_mid(A.xf, i), yc = tr_mid(A.yf, j);
+                    const double wu = tr_sample<T>(A, t, A.u, 0, x, y, i, j, xc, yc);
+                    const double wv = tr_sample<T>(A, t, A.v, 1, x, y, i, j, xc, yc);
+                    if (MODE == 0) {
+                        A.su[p] = wu;
+                        A.sv[p] = wv;
+                        ns = 0;
+                    } else if (isfinite(wu) && isfinite(wv)) {
+                        double xn, yn;
+                        if (sf & 4) {
+                            xn = tr_euler(x, A.dt, wu);
+                            yn = tr_euler(y, A.dt, wv);
+                        } else {
+                            xn = tr_ab2(x, A.dt, wu, A.wu[p]);
+                            yn = tr_ab2(y, A.dt, wv, A.wv[p]);
+                        }
+                        if (isfinite(xn) && isfinite(yn)) {
+                            const int ip = tr_locate(A.xf, g.nx, A.rhx, xn), jp = tr_locate(A.yf, g.ny, A.rhy, yn);
+                            bool live = ip >= 0 && ip < g.nx && jp >= 0 && jp < g.ny;
+                            if (live) live = T(g, ip, jp).cell();
+                            if (live) {
+                                age = A.age[p] + A.dt;
+                                A.x[p] = xn;
+                                A.y[p] = yn;
+                                A.wu[p] = wu;
+                                A.wv[p] = wv;
+                                A.age[p] = age;
+                                ns = 0;
+                            } else {
+                                const int di = (ip > i) - (ip < i), dj = (jp > j) - (jp < j);
+                                int face = -1;
+                                if (di != 0 && !t.in(di, 0)) face = di > 0 ? 1 : 0;
+                                else if (dj != 0 && !t.in(0, dj)) face = dj > 0 ? 3 : 2;
+                                if (face >= 0 && ((A.exitm >> tr_edge(t, face)) & 1u)) ns = 1;
+                            }
+                        }
+                    }
+                }
+            }
+            if (MODE == 0 && !ok) {
+                A.su[p] = NAN;
+                A.sv[p] = NAN;
+            }
+            if (MODE != 0) {
+                state = ns;
+                if (ns != 0 || (sf & 4)) A.st[p] = ns;   // (a live particle's word changes only to clear its fresh bit)
+            }
+        } else if (MODE == 0) {
+            A.su[p] = A.wu[p];
+            A.sv[p] = A.wv[p];
+        }
+        if (MODE == 2) {
+            cnt[state] += 1.0;
+            if (state == 0) am[0] = fmin(am[0], -age);
+        }
+    }
+    if (MODE == 2) {
+        block_reduce_sum<3>(cnt, A.part + 3 * (size_t)blockIdx.x);
+        block_reduce_min<1>(am, A.part + 3 * (size_t)gridDim.x + blockIdx.x);
+    }
+}
+
+int tracer_blocks(int64_t n) { return (int)std::min<int64_t>((n + 255) / 256, 4096); }
+int launch_tracer(const TracerArgs& A, int mode, hipStream_t st) {
+    if (A.n <= 0 || A.g.nxl != A.g.nx || mode < 0 || mode > 2) return -1;
+    const dim3 grid(tracer_blocks(A.n));
+    const bool m = A.g.fc != nullptr;
+    void (*const kern[2][3])(TracerArgs) = {{k_tracer<TopoRect, 0>, k_tracer<TopoRect, 1>, k_tracer<TopoRect, 2>},
+                                            {k_tracer<TopoMask, 0>, k_tracer<TopoMask, 1>, k_tracer<TopoMask, 2>}};
+    void (*const k)(TracerArgs) = kern[m][mode];
+    NS_LAUNCH(k, grid, dim3(256), 0, st, A);
+    return (int)grid.x;
+}
+
 template <int K>
 static int launch_cell_s(const Knobs& kn, CellStreamArgs A, hipStream_t st) {
     A.nsj = (A.g.ny + SW - 1) / SW;

@@ -402,6 +402,19 @@ struct ns_solver {
         double *part = nullptr, *ppart = nullptr, *scal = nullptr, *hs = nullptr;
         int ncap = 0, ldv = 0;
     } dv;
+    // tracer particles (ns_tracers_enable; DESIGN.md 4 "Tracers"): nothing below exists without them.  SoA planes of
+    // `cap` particles (x, y, wu, wv, age, then the int32 state words), the face tables xf | yf with their host copies
+    // (the seed check), partials, four count slots (live, exited, stuck, -max age) and their pinned mirror of its
+    // own; su / sv (ns_tracers_sample's output) on first use
+    struct Tracers {
+        enum { NSLOT = 4 };
+        bool on = false;
+        int64_t cap = 0, n = 0;
+        double *mem = nullptr, *smp = nullptr, *tab = nullptr;
+        double *part = nullptr, *scal = nullptr, *hs = nullptr;
+        std::vector<double> xf, yf;
+        nsg::TracerArgs a{};
+    } tr;
 };
 
 namespace {
@@ -3324,6 +3337,26 @@ int scalar_end(ns_solver* s) {
     return 0;
 }
 
+// ---------------- tracer particles (ns_tracers_enable; DESIGN.md 4 "Tracers")
+// one advance of the particles by dt in the planes U, V hold now (inside a step: u^n, v^n, which K1 leaves there in the
+// deferred-K5 path too), on the solver's stream; count: the fates' counts and the largest live age reduced into the
+// tracers' own slots behind it (no slot of the step's is touched, no host sync)
+int tracer_advance(ns_solver* s, double dt, bool count) {
+    auto& q = s->tr;
+    q.a.g = s->g;   // (an edge profile set since the last launch changes the geometry's table pointers)
+    q.a.u = s->arr[NS_ARR_U];
+    q.a.v = s->arr[NS_ARR_V];
+    q.a.n = q.n;
+    q.a.dt = dt;
+    Timing::Scope iv;
+    TCHK(s->tm.open(iv, nsg::T_TRACER, s->timing));
+    const int nb = nsg::launch_tracer(q.a, count ? 2 : 1, s->st);
+    if (nb < 0) { set_err("the tracer kernel's launch was refused"); return NS_EHIP; }
+    TCHK(iv.close());
+    if (count) nsg::launch_reduce_sum_min(q.part, nb, 3, q.scal, q.part + 3 * (size_t)nb, nb, 1, q.scal + 3, s->st);
+    return 0;
+}
+
 int check_arr(ns_solver* s, int which) {
     if (!s) { set_err("null solver"); return NS_EINVAL; }
     if (which < 0 || which >= NS_NUM_ARR) { set_err("bad array index %d", which); return NS_EINVAL; }
@@ -4145,6 +4178,9 @@ void ns_destroy(ns_solver* s) {
     for (double* q : {s->dv.p, s->dv.w, s->dv.d, s->dv.psi, s->dv.base, s->dv.part, s->dv.ppart, s->dv.scal})
         if (q) (void)hipFree(q);
     if (s->dv.hs) (void)hipHostFree(s->dv.hs);
+    for (double* q : {s->tr.mem, s->tr.smp, s->tr.tab, s->tr.part, s->tr.scal})
+        if (q) (void)hipFree(q);
+    if (s->tr.hs) (void)hipHostFree(s->tr.hs);
     if (s->comm) (void)ncclCommDestroy(s->comm);
     if (s->mev) (void)hipEventDestroy(s->mev);
     if (s->mm_host) (void)hipHostFree(s->mm_host);
@@ -4214,6 +4250,9 @@ static int step_body_(ns_solver* s, ns_stats& st) {
     // the passive scalar sees u^n, v^n as K1 does (which wrote them in the deferred-K5 path): its right-hand side
     // and first batch of sweeps here, their residual read after the velocities' Helmholtz check
     if (s->sc.on) CHK(scalar_begin(s));
+    // the tracer particles move in u^n, v^n too: the same placement, one launch (and its counts' reduction) on the
+    // stream before the Helmholtz passes overwrite the planes
+    if (s->tr.on && s->tr.n > 0) CHK(tracer_advance(s, s->dt, true));
     // Helmholtz initial guess: u^n.  (The previous step's u* -- kept by correct() in TMPU/TMPV --
     // was measured worse during the cavity's start-up transient: 14.7 vs 11 sweeps/step at 4096^2.)
     // rhs ghost rows (a checked pair pass and the 3-sweep pass read ib-5): multi-rank passes take them with
@@ -4475,6 +4514,197 @@ int ns_derive(ns_solver* s, const ns_derived* out, ns_derived_stats* st) {
     r.psi_min = o.psi ? h[9] : NAN;
     r.psi_max = o.psi ? -h[10] : NAN;
     if (st) *st = r;
+    return 0;
+}
+
+// ---------------- tracer particles ("Tracers"): the entry points.  One rank; planes, tables, partials and
+// slots of their own
+static int tracers_on(ns_solver* s, const char* who) {
+    if (!s) { set_err("null solver"); return NS_EINVAL; }
+    if (!s->tr.on) { set_err("%s: tracers are not enabled (ns_tracers_enable)", who); return NS_EINVAL; }
+    return 0;
+}
+
+int ns_tracers_enable(ns_solver* s, int64_t capacity) {
+    if (!s) { set_err("null solver"); return NS_EINVAL; }
+    if (s->tr.on) { set_err("ns_tracers_enable: tracers are already enabled"); return NS_EINVAL; }
+    if (capacity <= 0) { set_err("ns_tracers_enable: capacity %lld is not positive", (long long)capacity); return NS_EINVAL; }
+    if (s->nranks > 1) {
+        set_err("ns_tracers_enable: nranks > 1 is not supported (particles would migrate between slabs)");
+        return NS_EINVAL;
+    }
+    HIPCHK(hipSetDevice(s->device));
+    using Q = ns_solver::Tracers;
+    auto& q = s->tr;
+    const nsg::Geo& g = s->g;
+    // the faces from the spacings the solver holds, summed one by one: xf[i + 1] = xf[i] + hx[i]
+    std::vector<double> hx(g.nx), hy(g.ny);
+    HIPCHK(hipMemcpy(hx.data(), s->c.hx, (size_t)g.nx * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(hy.data(), s->c.hy, (size_t)g.ny * sizeof(double), hipMemcpyDeviceToHost));
+    auto faces = [](const std::vector<double>& h, std::vector<double>& f) {
+        f.assign(h.size() + 1, 0.0);
+        for (size_t i = 0; i < h.size(); i++) f[i + 1] = f[i] + h[i];
+        for (double v : h)
+            if (v != h[0]) return 0.0;
+        return (double)h.size() / f.back();   // uniform: cells per unit length
+    };
+    const double rhx = faces(hx, q.xf), rhy = faces(hy, q.yf);
+    const size_t cap = (size_t)capacity;
+    CHK(dev_alloc(s, &q.mem, cap * (5 * sizeof(double) + sizeof(int32_t)), true, "tracer planes"));
+    std::vector<double> tab(q.xf);
+    tab.insert(tab.end(), q.yf.begin(), q.yf.end());
+    CHK(dev_upload(s, &q.tab, tab, "tracer face tables"));
+    CHK(dev_alloc(s, &q.part, (size_t)nsg::tracer_blocks(capacity) * 4 * sizeof(double), false, "tracer partials"));
+    CHK(dev_alloc(s, &q.scal, Q::NSLOT * sizeof(double), true, "tracer slots"));
+    if (hipHostMalloc(&q.hs, Q::NSLOT * sizeof(double), hipHostMallocDefault) != hipSuccess) { set_err("hipHostMalloc failed"); return NS_ENOMEM; }
+    nsg::TracerArgs& a = q.a;
+    a = nsg::TracerArgs{};
+    a.xf = q.tab;
+    a.yf = q.tab + g.nx + 1;
+    a.rhx = rhx;
+    a.rhy = rhy;
+    a.x = q.mem;
+    a.y = a.x + cap;
+    a.wu = a.y + cap;
+    a.wv = a.wu + cap;
+    a.age = a.wv + cap;
+    a.st = reinterpret_cast<int32_t*>(a.age + cap);
+    a.part = q.part;
+    // the edges a particle leaves the domain through (the rest are walls): per side on a rectangle, per edge on a mask
+    auto open_edge = [&](int e) { return s->eprof[e].type == NS_BC_NEUMANN || s->eprof[e].type == NS_BC_INLET_UNI; };
+    if (g.fc) {
+        for (int e = 0; e < (int)s->eprof.size() && e < nsg::MAX_EDGES; e++)
+            if (open_edge(e)) a.exitm |= 1u << e;
+    } else {
+        for (int k = 0; k < 4; k++)
+            if (open_edge(s->side_edge[k])) a.exitm |= 1u << k;
+    }
+    q.cap = capacity;
+    q.n = 0;
+    q.on = true;
+    return 0;
+}
+
+int ns_tracers_add(ns_solver* s, const double* x, const double* y, int64_t n) {
+    CHK(tracers_on(s, "ns_tracers_add"));
+    auto& q = s->tr;
+    if (n < 0 || (n > 0 && (!x || !y))) { set_err("ns_tracers_add: %lld seeds with a NULL coordinate array", (long long)n); return NS_EINVAL; }
+    if (n > q.cap - q.n) {
+        set_err("ns_tracers_add: %lld seeds on top of %lld exceed the capacity %lld", (long long)n, (long long)q.n, (long long)q.cap);
+        return NS_EINVAL;
+    }
+    const int nx = s->g.nx, ny = s->g.ny;
+    auto cell = [](const std::vector<double>& f, double v) {   // f[i] <= v < f[i + 1], or -1
+        if (!(v >= 0.0 && v < f.back())) return -1;
+        return (int)(std::upper_bound(f.begin(), f.end(), v) - f.begin()) - 1;
+    };
+    for (int64_t k = 0; k < n; k++) {
+        if (!std::isfinite(x[k]) || !std::isfinite(y[k])) {
+            set_err("ns_tracers_add: seed %lld (%g, %g) is not finite", (long long)k, x[k], y[k]);
+            return NS_EINVAL;
+        }
+        const int i = cell(q.xf, x[k]), j = cell(q.yf, y[k]);
+        if (i < 0 || i >= nx || j < 0 || j >= ny || (!s->cid.empty() && s->cid[(size_t)i * ny + j] < 0)) {
+            set_err("ns_tracers_add: seed %lld (%g, %g) is not in a domain cell", (long long)k, x[k], y[k]);
+            return NS_EINVAL;
+        }
+    }
+    if (n == 0) return 0;
+    HIPCHK(hipSetDevice(s->device));
+    const nsg::TracerArgs& a = q.a;
+    const size_t nb = (size_t)n * sizeof(double);
+    HIPCHK(hipMemcpyAsync(a.x + q.n, x, nb, hipMemcpyHostToDevice, s->st));
+    HIPCHK(hipMemcpyAsync(a.y + q.n, y, nb, hipMemcpyHostToDevice, s->st));
+    HIPCHK(hipMemsetAsync(a.wu + q.n, 0, nb, s->st));
+    HIPCHK(hipMemsetAsync(a.wv + q.n, 0, nb, s->st));
+    HIPCHK(hipMemsetAsync(a.age + q.n, 0, nb, s->st));
+    HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a.st + q.n), NS_TRACER_LIVE | 4, (size_t)n, s->st));   // (fresh)
+    HIPCHK(hipStreamSynchronize(s->st));   // (the caller owns x, y)
+    q.n += n;
+    return 0;
+}
+
+int ns_tracers_get(ns_solver* s, int64_t first, int64_t n, double* x, double* y, double* age, int32_t* state) {
+    CHK(tracers_on(s, "ns_tracers_get"));
+    auto& q = s->tr;
+    if (first < 0 || n < 0 || first > q.n || n > q.n - first) {
+        set_err("ns_tracers_get: the range [%lld, %lld) is outside [0, %lld)", (long long)first, (long long)(first + n), (long long)q.n);
+        return NS_EINVAL;
+    }
+    HIPCHK(hipSetDevice(s->device));
+    const nsg::TracerArgs& a = q.a;
+    const size_t nb = (size_t)n * sizeof(double);
+    if (n > 0) {
+        if (x) HIPCHK(hipMemcpyAsync(x, a.x + first, nb, hipMemcpyDeviceToHost, s->st));
+        if (y) HIPCHK(hipMemcpyAsync(y, a.y + first, nb, hipMemcpyDeviceToHost, s->st));
+        if (age) HIPCHK(hipMemcpyAsync(age, a.age + first, nb, hipMemcpyDeviceToHost, s->st));
+        if (state) HIPCHK(hipMemcpyAsync(state, a.st + first, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s->st));
+    }
+    HIPCHK(hipStreamSynchronize(s->st));
+    if (state)
+        for (int64_t k = 0; k < n; k++) state[k] &= 3;   // (without the fresh bit)
+    return 0;
+}
+
+int ns_tracers_sample(ns_solver* s, double* u, double* v) {
+    CHK(tracers_on(s, "ns_tracers_sample"));
+    CHK(materialize(s));
+    auto& q = s->tr;
+    if (q.n == 0) return 0;
+    HIPCHK(hipSetDevice(s->device));
+    nsg::set_compute_cus(s->compute_cus);
+    if (!q.smp) CHK(dev_alloc(s, &q.smp, (size_t)q.cap * 2 * sizeof(double), true, "tracer samples"));
+    q.a.g = s->g;
+    q.a.u = s->arr[NS_ARR_U];
+    q.a.v = s->arr[NS_ARR_V];
+    q.a.n = q.n;
+    q.a.su = q.smp;
+    q.a.sv = q.smp + q.cap;
+    if (nsg::launch_tracer(q.a, 0, s->st) < 0) { set_err("the tracer kernel's launch was refused"); return NS_EHIP; }
+    const size_t nb = (size_t)q.n * sizeof(double);
+    if (u) HIPCHK(hipMemcpyAsync(u, q.a.su, nb, hipMemcpyDeviceToHost, s->st));
+    if (v) HIPCHK(hipMemcpyAsync(v, q.a.sv, nb, hipMemcpyDeviceToHost, s->st));
+    HIPCHK(hipStreamSynchronize(s->st));
+    return 0;
+}
+
+int ns_tracers_advance(ns_solver* s, double dt, int32_t steps) {
+    CHK(tracers_on(s, "ns_tracers_advance"));
+    if (!std::isfinite(dt)) { set_err("ns_tracers_advance: dt = %g is not finite", dt); return NS_EINVAL; }
+    if (steps < 0) { set_err("ns_tracers_advance: steps = %d is negative", steps); return NS_EINVAL; }
+    CHK(materialize(s));
+    if (s->tr.n == 0 || steps == 0) return 0;
+    HIPCHK(hipSetDevice(s->device));
+    nsg::set_compute_cus(s->compute_cus);
+    (void)s->tm.drain(nsg::tbit(nsg::T_TRACER), nullptr);   // (an earlier advance's intervals nobody asked for)
+    for (int k = 0; k < steps; k++) CHK(tracer_advance(s, dt, k == steps - 1));
+    return 0;
+}
+
+int ns_tracers_reset(ns_solver* s) {
+    CHK(tracers_on(s, "ns_tracers_reset"));
+    HIPCHK(hipSetDevice(s->device));
+    s->tr.n = 0;
+    HIPCHK(hipMemsetAsync(s->tr.scal, 0, ns_solver::Tracers::NSLOT * sizeof(double), s->st));
+    (void)s->tm.drain(nsg::tbit(nsg::T_TRACER), nullptr);
+    return 0;
+}
+
+int ns_tracers_last(ns_solver* s, ns_tracer_stats* out) {
+    CHK(tracers_on(s, "ns_tracers_last"));
+    if (!out) { set_err("ns_tracers_last: out is NULL"); return NS_EINVAL; }
+    HIPCHK(hipSetDevice(s->device));
+    auto& q = s->tr;
+    HIPCHK(hipMemcpyAsync(q.hs, q.scal, ns_solver::Tracers::NSLOT * sizeof(double), hipMemcpyDeviceToHost, s->st));
+    HIPCHK(hipStreamSynchronize(s->st));
+    ns_tracer_stats r{};
+    TCHK(s->tm.drain(nsg::tbit(nsg::T_TRACER), nullptr, nullptr, nullptr, &r));
+    r.n = q.n;
+    r.live = (int64_t)q.hs[0];
+    r.exited = (int64_t)q.hs[1];
+    r.stuck = (int64_t)q.hs[2];
+    r.age_max = r.live > 0 ? -q.hs[3] : 0.0;
+    *out = r;
     return 0;
 }
 

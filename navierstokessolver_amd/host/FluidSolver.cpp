@@ -24,6 +24,7 @@ struct Options {
     int device = 0;
     bool do_export = true;
     bool derived = false;   // -derived: Derived_<iter>.csv beside every export, one summary line after the last step
+    std::string tracers;    // -tracers seeds.csv: particles carried by the step, Tracers_<iter>.csv beside every export
 };
 Options g_opt;
 
@@ -49,6 +50,8 @@ PetscErrorCode PetscInitialize(int* argc, char*** argv, const char*, const char*
             ns_export_files = false;   // CellCenters.csv too (Grid.cpp)
         } else if (!std::strcmp(a, "-derived")) {
             g_opt.derived = true;
+        } else if (!std::strcmp(a, "-tracers")) {
+            g_opt.tracers = next();
         } else {
             keep.push_back((*argv)[k]);  // positional arguments (grid file, sim file) stay
         }
@@ -263,6 +266,37 @@ void write_derived_csv(int iter, Grid& g, const vector<double>& w, const vector<
         }
 }
 
+// -tracers: the seeds file, one "x,y" line per particle in the grid's own coordinates (lines that do not parse --
+// a header -- are skipped); false if the file cannot be read
+bool read_seeds(const std::string& fname, vector<double>& x, vector<double>& y) {
+    ifstream in{fname};
+    if (!in) return false;
+    string line;
+    while (getline(in, line)) {
+        double a, b;
+        if (std::sscanf(line.c_str(), " %lf , %lf", &a, &b) == 2) x.push_back(a), y.push_back(b);
+    }
+    return true;
+}
+
+// ... and the particles beside FlowData_<iter>.csv: id, position (the grid's coordinates again), age, NS_TRACER_* state
+void write_tracers_csv(int iter, ns_solver* gpu, int64_t n, double ox, double oy) {
+    vector<double> x(n), y(n), age(n);
+    vector<int32_t> state(n);
+    if (ns_tracers_get(gpu, 0, n, x.data(), y.data(), age.data(), state.data()) != 0) {
+        cout << "Tracers failed: " << ns_last_error() << "\n";
+        return;
+    }
+    char name[64];
+    std::snprintf(name, sizeof name, "Tracers_%d.csv", iter);
+    FILE* f = std::fopen(name, "w");
+    if (!f) return;
+    std::fprintf(f, "id,x,y,age,state\n");
+    for (int64_t k = 0; k < n; k++)
+        std::fprintf(f, "%lld,%.15g,%.15g,%.15g,%d\n", (long long)k, x[k] + ox, y[k] + oy, age[k], (int)state[k]);
+    std::fclose(f);
+}
+
 }  // namespace
 
 void FluidSolver::Solve() {
@@ -272,6 +306,19 @@ void FluidSolver::Solve() {
     const size_t n = (size_t)m.nx * m.ny;
     vector<double> u, v, phi;   // host copies for the export only (allocated on the first one)
     vector<double> dw, dd, dp;  // -derived: the device's vorticity, divergence, pressure
+    int64_t ntr = 0;            // -tracers: the particles seeded (0: none, or the option failed)
+    const double ox = grid->X[0], oy = grid->Y[0];   // (ns_grid_desc carries no origin: the library's box starts at 0, 0)
+    if (!g_opt.tracers.empty()) {
+        vector<double> sx, sy;
+        if (!read_seeds(g_opt.tracers, sx, sy) || sx.empty()) cout << "Tracers failed: no seeds in " << g_opt.tracers << "\n";
+        else {
+            for (size_t k = 0; k < sx.size(); k++) sx[k] -= ox, sy[k] -= oy;
+            if (ns_tracers_enable(m.gpu, (int64_t)sx.size()) == 0 &&
+                ns_tracers_add(m.gpu, sx.data(), sy.data(), (int64_t)sx.size()) == 0)
+                ntr = (int64_t)sx.size();
+            else cout << "Tracers failed: " << ns_last_error() << "\n";
+        }
+    }
     int iter = 1;
     do {
         ns_stats st{};
@@ -294,6 +341,7 @@ void FluidSolver::Solve() {
                 if (ns_derive(m.gpu, &out, nullptr) == 0) write_derived_csv(iter, *grid, dw, dd, dp);
                 else cout << "Derived fields failed: " << ns_last_error() << "\n";
             }
+            if (ntr > 0) write_tracers_csv(iter, m.gpu, ntr, ox, oy);
         }
         iter++;
     } while (m.p.dt * iter <= m.p.finalTime);
@@ -302,6 +350,13 @@ void FluidSolver::Solve() {
         if (ns_derive(m.gpu, nullptr, &ds) == 0)
             printf("derived: ke %.9e enstrophy %.9e div_max %.9e cfl %.9e\n", ds.ke, ds.enstrophy, ds.div_max, ds.cfl);
         else cout << "Derived fields failed: " << ns_last_error() << "\n";
+    }
+    if (ntr > 0) {
+        ns_tracer_stats ts{};
+        if (ns_tracers_last(m.gpu, &ts) == 0)
+            printf("tracers: n %lld live %lld exited %lld stuck %lld age_max %.9e\n", (long long)ts.n, (long long)ts.live,
+                   (long long)ts.exited, (long long)ts.stuck, ts.age_max);
+        else cout << "Tracers failed: " << ns_last_error() << "\n";
     }
     fflush(stdout);
     cout << "Solution Complete!\n";

@@ -81,6 +81,7 @@ class GpuSolver:
                          mg_omega)
         self._transport = host_transport  # keep the callbacks alive
         self._scalar = False
+        self._tracers = 0   # particles added so far (add_tracers / reset_tracers)
         h = ctypes.c_void_p()
         L.check(L.lib().ns_create(ctypes.byref(desc), ctypes.byref(prm), ctypes.byref(h)))
         self._h = h
@@ -202,6 +203,54 @@ class GpuSolver:
         st = L.NsDerivedStats()
         L.check(L.lib().ns_derive(self._h, ctypes.byref(out), ctypes.byref(st)))
         return {**arrs, **st.as_dict()}
+
+    # ---- tracer particles (ns_tracers_*: one rank)
+    def enable_tracers(self, capacity: int) -> None:
+        """Room for `capacity` Lagrangian particles; once per solver.  While particles exist, every step() /
+        step_async() carries them by dt in u^n, v^n on the device."""
+        L.check(L.lib().ns_tracers_enable(self._h, int(capacity)))
+        self._tracers = 0
+
+    def add_tracers(self, x, y) -> None:
+        """Append particles at (x, y): physical coordinates relative to the bounding box's lower-left corner, each in
+        a domain cell.  All or nothing; indices are stable, so adding between steps draws streaklines."""
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float64).ravel())
+        y = np.ascontiguousarray(np.asarray(y, dtype=np.float64).ravel())
+        if x.size != y.size:
+            raise ValueError(f"{x.size} x coordinates, {y.size} y coordinates")
+        L.check(L.lib().ns_tracers_add(self._h, _dptr(x), _dptr(y), x.size))
+        self._tracers += x.size
+
+    def tracers(self, first: int = 0, n: int | None = None) -> dict:
+        """x, y, age, state (NS_TRACER_LIVE / EXITED / STUCK) of particles [first, first + n) (default: all of them)
+        and the counts after the latest advance under ns_tracer_stats' field names."""
+        st = self.tracer_stats()
+        n = st["n"] - first if n is None else int(n)
+        x, y, age = (np.empty(max(n, 0), dtype=np.float64) for _ in range(3))
+        state = np.empty(max(n, 0), dtype=np.int32)
+        L.check(L.lib().ns_tracers_get(self._h, int(first), n, _dptr(x), _dptr(y), _dptr(age),
+                                       state.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+        return {"x": x, "y": y, "age": age, "state": state, **st}
+
+    def tracer_stats(self) -> dict:
+        st = L.NsTracerStats()
+        L.check(L.lib().ns_tracers_last(self._h, ctypes.byref(st)))
+        return st.as_dict()
+
+    def sample_tracers(self):
+        """(u, v) at the particles' current positions in the current fields."""
+        n = self._tracers   # (not tracer_stats(): ns_tracers_last hands the latest advance's kernel time out once)
+        u, v = np.empty(n, dtype=np.float64), np.empty(n, dtype=np.float64)
+        L.check(L.lib().ns_tracers_sample(self._h, _dptr(u), _dptr(v)))
+        return u, v
+
+    def advance_tracers(self, dt: float, steps: int = 1) -> None:
+        """`steps` advances of dt in the current u, v held fixed (pathlines of a steady field)."""
+        L.check(L.lib().ns_tracers_advance(self._h, float(dt), int(steps)))
+
+    def reset_tracers(self) -> None:
+        L.check(L.lib().ns_tracers_reset(self._h))
+        self._tracers = 0
 
     # ---- passive scalar (ns_scalar_*: one rank's rectangle)
     def enable_scalar(self, pe: float, bc) -> None:
