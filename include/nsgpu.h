@@ -408,6 +408,59 @@ int  ns_tracers_advance(ns_solver* s, double dt, int32_t steps);
 int  ns_tracers_reset(ns_solver* s);
 int  ns_tracers_last(ns_solver* s, ns_tracer_stats* out);
 
+/* ---- running flow statistics: time means and Reynolds stresses accumulated by the time step ----
+ * Optional running means of u, v (and on request the pressure P and the carried scalar T) and their central
+ * co-moment sums, kept on the device ("Flow statistics"; the normative statement is tests/stats_ref.py).
+ * Sample number n + 1 of a source plane x updates, with w = 1.0 / (n + 1) formed on the host in double:
+ *   dx = x - xm     xm' = xm + w dx     Sxx' = Sxx + dx (x - xm')     Sxy' = Sxy + dx (y - ym')
+ * (dx from x's old mean, ym' y's new one).  Handed out: the means as they stand and S * (1.0 / n), the population
+ * covariances <x'y'>.  Co-moments kept with NS_AVG_SECOND: uu, vv, uv; pp with NS_AVG_PRESSURE; TT, uT, vT with
+ * NS_AVG_SCALAR; no others.
+ *   in the step:   step k since enable / reset (k = 0, 1, ..) with k % every == 0 samples the state the step starts
+ *                  from -- u^n, v^n, phi^n, T^n -- on the solver's stream right behind K1, in ns_step and ns_step_async
+ *                  alike; no host sync is added.  N steps at every = 1 sample the states 0 .. N - 1.
+ *   ns_avg_sample: samples the current fields between steps (a deferred correction is settled first, as by
+ *                  ns_get_array): how a caller adds the final state.
+ *   ns_avg_reset:  n = 0, steps = 0, every plane zero: the spin-up cut-off.
+ *   P:             ns_derive's pressure phi - dt / (2 re) L phi, written by that cell pass into a plane of the
+ *                  statistics' own: pressure statistics cost one extra pass of 24 + 8 B/cell per sample.
+ * A solver that never enables them runs exactly the launches it ran before.  The planes are allocated by
+ * ns_avg_enable (not counted by ns_device_bytes).
+ * ns_avg_get:  the nx_local x ny bounding-box plane as ns_get_array's, exactly 0 outside a polygon; all 0 while
+ *              n == 0; synchronises.
+ * ns_avg_last: n, the steps since enable / reset and the sample passes' kernel time since the last call
+ *              (timing == 1; handed out once); synchronises.
+ * NS_EINVAL (the message names the cause): a null solver or descriptor, every < 1, unknown flag bits, enabling twice,
+ * any other ns_avg_* call before ns_avg_enable, NS_AVG_SCALAR without a scalar, nranks > 1, an unknown `which`, a
+ * `which` whose plane this solver does not accumulate.  Additive to ABI 9. */
+#define NS_AVG_SECOND   1   /* + uu, vv, uv (and pp / TT, uT, vT of the sources asked for) */
+#define NS_AVG_PRESSURE 2   /* + P */
+#define NS_AVG_SCALAR   4   /* + T: needs ns_scalar_enable before ns_avg_enable */
+typedef struct ns_avg_desc  { int32_t every; int32_t flags; } ns_avg_desc;
+typedef struct ns_avg_stats {
+    int64_t n;                   /* samples taken since enable / reset */
+    int64_t steps;               /* steps since enable / reset */
+    double  t_kernel_ms;         /* the sample passes' kernels since the last ns_avg_last (timing == 1) */
+    int32_t n_kernels;           /* one per sample, two with NS_AVG_PRESSURE (the derived pass) */
+} ns_avg_stats;
+#define NS_AVG_U   0   /* the means */
+#define NS_AVG_V   1
+#define NS_AVG_P   2
+#define NS_AVG_T   3
+#define NS_AVG_UU  4   /* the covariances <x'y'> */
+#define NS_AVG_VV  5
+#define NS_AVG_UV  6
+#define NS_AVG_PP  7
+#define NS_AVG_TT  8
+#define NS_AVG_UT  9
+#define NS_AVG_VT 10
+#define NS_AVG_NUM 11
+int  ns_avg_enable(ns_solver* s, const ns_avg_desc* d);   /* once per solver */
+int  ns_avg_reset(ns_solver* s);
+int  ns_avg_sample(ns_solver* s);
+int  ns_avg_get(ns_solver* s, int which, double* plane);
+int  ns_avg_last(ns_solver* s, ns_avg_stats* out);
+
 /* ---- host-side helpers (no GPU needed) ---- */
 /* the face averages of the parabola 6 s (1 - s) * mean over the faces k0 <= k < k1 of spacings h[0..n) (s runs 0..1
  * from face k0's lower end to face k1-1's upper end), 0 elsewhere: the average over [sa, sb] is

@@ -132,6 +132,24 @@ class NsTracerStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+NS_AVG_SECOND, NS_AVG_PRESSURE, NS_AVG_SCALAR = 1, 2, 4
+(NS_AVG_U, NS_AVG_V, NS_AVG_P, NS_AVG_T, NS_AVG_UU, NS_AVG_VV, NS_AVG_UV, NS_AVG_PP, NS_AVG_TT, NS_AVG_UT,
+ NS_AVG_VT) = range(11)
+NS_AVG_NUM = 11
+
+
+class NsAvgDesc(ctypes.Structure):
+    _fields_ = [("every", ctypes.c_int32), ("flags", ctypes.c_int32)]
+
+
+class NsAvgStats(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_int64), ("steps", ctypes.c_int64), ("t_kernel_ms", ctypes.c_double),
+                ("n_kernels", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _P = ctypes.c_void_p
 _D = ctypes.POINTER(ctypes.c_double)
 SIGNATURES = {
@@ -167,6 +185,11 @@ SIGNATURES = {
     "ns_tracers_advance": (ctypes.c_int, [_P, ctypes.c_double, ctypes.c_int32]),
     "ns_tracers_reset": (ctypes.c_int, [_P]),
     "ns_tracers_last": (ctypes.c_int, [_P, ctypes.POINTER(NsTracerStats)]),
+    "ns_avg_enable": (ctypes.c_int, [_P, ctypes.POINTER(NsAvgDesc)]),
+    "ns_avg_reset": (ctypes.c_int, [_P]),
+    "ns_avg_sample": (ctypes.c_int, [_P]),
+    "ns_avg_get": (ctypes.c_int, [_P, ctypes.c_int, _D]),
+    "ns_avg_last": (ctypes.c_int, [_P, ctypes.POINTER(NsAvgStats)]),
     "ns_parabolic_profile": (ctypes.c_int, [_D, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, _D]),
     "ns_slab_range": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                      ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),

@@ -173,6 +173,19 @@ struct TracerArgs {
 // mode 0: sample only, 1: advance, 2: advance and count; returns the block count (tracer_blocks(n)), -1 if refused
 int tracer_blocks(int64_t n);
 int launch_tracer(const TracerArgs& A, int mode, hipStream_t st);
+// running flow statistics (ns_avg_*; DESIGN.md 4, "Flow statistics"; ns_avg.hip): one sample of the source planes
+// into the running means and central co-moment sums, a pointwise pass over rows [0, nxl) x columns [0, ny) of
+// ld-strided planes (no topology, no ghost rows).  Sources in the order u, v, then T (has_t), then P (nsrc counts
+// them: 2 .. 4); S with `second`: uu, vv, uv, then TT, uT, vT (has_t), then pp (a P source) -- the rest unused
+struct MomArgs {
+    const double* src[4];
+    double* mean[4];
+    double* S[7];
+    double w;          // 1.0 / (n + 1), formed on the host: the kernel does no division
+    int nxl, ny, ld;
+};
+// k_moments<NSRC, SECOND, HAS_T>; -1: no such instantiation, or a plane not 16-byte aligned
+int launch_moments(const MomArgs& A, int nsrc, bool second, bool has_t, hipStream_t st);
 // K2: fused red-black SOR sweep of (I - a L_V) on u and v, (u,v) -> (uo,vo);
 //     residual^2 partials of the input if part != null: u at part[0..n), v at part[n..2n), n returned
 int launch_helm_sweep(const Knobs& kn, const Geo& g, const Coef& c, double alpha, double omega, const double* u, const double* v,

@@ -415,6 +415,20 @@ struct ns_solver {
         std::vector<double> xf, yf;
         nsg::TracerArgs a{};
     } tr;
+    // running flow statistics (ns_avg_enable; DESIGN.md 4 "Flow statistics"): nothing below exists without them.
+    // mem: the means and co-moment sums accumulated (nxl x ld each, no ghost rows; plane[which], null: not kept) and,
+    // with NS_AVG_PRESSURE, the sample's own pressure plane P behind them; ppart: the derived pass's partials, of
+    // its own, so that no slot a step or ns_derive reads is touched.  n, steps: host counters
+    struct Averages {
+        bool on = false;
+        int every = 1, flags = 0, nsrc = 2;
+        int64_t n = 0, steps = 0;
+        size_t nplanes = 0;
+        double *mem = nullptr, *P = nullptr, *ppart = nullptr;
+        double* plane[NS_AVG_NUM] = {};
+        nsg::MomArgs a{};
+        ns_avg_stats acc{};      // the drained sample intervals nobody has asked for yet
+    } av;
 };
 
 namespace {
@@ -3357,6 +3371,39 @@ int tracer_advance(ns_solver* s, double dt, bool count) {
     return 0;
 }
 
+// ---------------- running flow statistics (ns_avg_enable; DESIGN.md 4 "Flow statistics")
+// one sample of the planes U, V (PHI, T) hold now into the running means and co-moment sums, on the solver's stream
+// (inside a step: u^n, v^n, phi^n, T^n right behind K1, which leaves them there in the deferred-K5 path too).  The
+// pressure first, by the derived fields' cell pass storing P only, into the statistics' own plane.  n and w are
+// host-side: no sync, no readback
+int avg_sample(ns_solver* s) {
+    auto& q = s->av;
+    nsg::MomArgs& a = q.a;
+    const bool has_t = (q.flags & NS_AVG_SCALAR) != 0, has_p = (q.flags & NS_AVG_PRESSURE) != 0;
+    a.src[0] = s->arr[NS_ARR_U];
+    a.src[1] = s->arr[NS_ARR_V];
+    if (has_t) a.src[2] = s->sc.T;   // (the scalar's current plane: its sweeps swap T and its partner)
+    if (has_p) {
+        Timing::Scope iv;
+        TCHK(s->tm.open(iv, nsg::T_AVG, s->timing));
+        const int nb = nsg::launch_derived(s->k, s->g, s->c, s->dt / (2 * s->re), s->arr[NS_ARR_U], s->arr[NS_ARR_V],
+                                           s->arr[NS_ARR_PHI], q.P, nullptr, nullptr, q.ppart, s->st);
+        if (nb < 0) { set_err("flow statistics: the pressure pass's launch was refused"); return NS_EHIP; }
+        TCHK(iv.close());
+        a.src[q.nsrc - 1] = q.P;
+    }
+    a.w = 1.0 / (double)(q.n + 1);
+    Timing::Scope iv;
+    TCHK(s->tm.open(iv, nsg::T_AVG, s->timing));
+    if (nsg::launch_moments(a, q.nsrc, (q.flags & NS_AVG_SECOND) != 0, has_t, s->st) < 0) {
+        set_err("flow statistics: the moments kernel's launch was refused");
+        return NS_EHIP;
+    }
+    TCHK(iv.close());
+    q.n++;
+    return 0;
+}
+
 int check_arr(ns_solver* s, int which) {
     if (!s) { set_err("null solver"); return NS_EINVAL; }
     if (which < 0 || which >= NS_NUM_ARR) { set_err("bad array index %d", which); return NS_EINVAL; }
@@ -4181,6 +4228,8 @@ void ns_destroy(ns_solver* s) {
     for (double* q : {s->tr.mem, s->tr.smp, s->tr.tab, s->tr.part, s->tr.scal})
         if (q) (void)hipFree(q);
     if (s->tr.hs) (void)hipHostFree(s->tr.hs);
+    for (double* q : {s->av.mem, s->av.ppart})
+        if (q) (void)hipFree(q);
     if (s->comm) (void)ncclCommDestroy(s->comm);
     if (s->mev) (void)hipEventDestroy(s->mev);
     if (s->mm_host) (void)hipHostFree(s->mm_host);
@@ -4245,8 +4294,16 @@ static int step_body(ns_solver* s, ns_stats& st) {
 
 static int step_body_(ns_solver* s, ns_stats& st) {
     // (intervals a standalone kernel call or a failed step left behind are dropped; K5's wait for their drain below)
-    (void)s->tm.drain(~nsg::tbit(nsg::T_K5), nullptr);
+    // (the flow statistics' intervals are kept: they add up until ns_avg_last asks)
+    (void)s->tm.drain(~(nsg::tbit(nsg::T_K5) | nsg::tbit(nsg::T_AVG)), nullptr);
     CHK(rhs(s, true));                                             // ConstructRHS_V       (:546)
+    // the flow statistics sample the state the step starts from -- u^n, v^n, phi^n, T^n -- directly behind K1 (after
+    // it U, V hold u^n, v^n in the deferred-K5 path too), ahead of the scalar's first batch, which swaps T^n away,
+    // and of the Helmholtz passes
+    if (s->av.on) {
+        if (s->av.steps % s->av.every == 0) CHK(avg_sample(s));
+        s->av.steps++;
+    }
     // the passive scalar sees u^n, v^n as K1 does (which wrote them in the deferred-K5 path): its right-hand side
     // and first batch of sweeps here, their residual read after the velocities' Helmholtz check
     if (s->sc.on) CHK(scalar_begin(s));
@@ -4269,6 +4326,7 @@ static int step_body_(ns_solver* s, ns_stats& st) {
     // (helm_solve's last residual check synchronised the stream: behind the Helmholtz passes -- per component, 24
     // B/cell --, K1, the wall bands and the previous step's K5)
     TCHK(s->tm.drain(nsg::tbit(nsg::T_HELM) | nsg::tbit(nsg::T_K1) | nsg::tbit(nsg::T_BAND) | nsg::tbit(nsg::T_K5), &st));
+    if (s->av.on) TCHK(s->tm.drain(nsg::tbit(nsg::T_AVG), nullptr, nullptr, nullptr, nullptr, &s->av.acc));
     if (!s->k3_spec) CHK(divergence(s));                           // ConstructRHS_phi + mean (:549-550)
     s->k3_spec = 0;
     CHK(consistent_rhs(s));                                        // stretched grids only
@@ -4704,6 +4762,130 @@ int ns_tracers_last(ns_solver* s, ns_tracer_stats* out) {
     r.exited = (int64_t)q.hs[1];
     r.stuck = (int64_t)q.hs[2];
     r.age_max = r.live > 0 ? -q.hs[3] : 0.0;
+    *out = r;
+    return 0;
+}
+
+// ---------------- running flow statistics ("Flow statistics"): the entry points.  One rank; planes and
+// partials of their own
+static int avg_on(ns_solver* s, const char* who) {
+    if (!s) { set_err("null solver"); return NS_EINVAL; }
+    if (!s->av.on) { set_err("%s: flow statistics are not enabled (ns_avg_enable)", who); return NS_EINVAL; }
+    return 0;
+}
+
+int ns_avg_enable(ns_solver* s, const ns_avg_desc* d) {
+    if (!s) { set_err("null solver"); return NS_EINVAL; }
+    if (!d) { set_err("ns_avg_enable: the descriptor is NULL"); return NS_EINVAL; }
+    if (s->av.on) { set_err("ns_avg_enable: flow statistics are already enabled"); return NS_EINVAL; }
+    if (d->every < 1) { set_err("ns_avg_enable: every = %d is less than 1", d->every); return NS_EINVAL; }
+    const int known = NS_AVG_SECOND | NS_AVG_PRESSURE | NS_AVG_SCALAR;
+    if (d->flags & ~known) { set_err("ns_avg_enable: unknown flag bits 0x%x", (unsigned)(d->flags & ~known)); return NS_EINVAL; }
+    if (s->nranks > 1) { set_err("ns_avg_enable: nranks > 1 is not supported (the pressure comes from ns_derive, one rank)"); return NS_EINVAL; }
+    if ((d->flags & NS_AVG_SCALAR) && !s->sc.on) {
+        set_err("ns_avg_enable: NS_AVG_SCALAR needs a scalar (ns_scalar_enable first)");
+        return NS_EINVAL;
+    }
+    HIPCHK(hipSetDevice(s->device));
+    auto& q = s->av;
+    const nsg::Geo& g = s->g;
+    const bool second = d->flags & NS_AVG_SECOND, has_p = d->flags & NS_AVG_PRESSURE, has_t = d->flags & NS_AVG_SCALAR;
+    // the planes kept, in the kernel's order: sources u, v, T, P; co-moments uu, vv, uv, TT, uT, vT, pp
+    int mean_of[4] = {NS_AVG_U, NS_AVG_V, -1, -1}, co_of[7] = {-1, -1, -1, -1, -1, -1, -1};
+    int nsrc = 2, nco = 0;
+    if (has_t) mean_of[nsrc++] = NS_AVG_T;
+    if (has_p) mean_of[nsrc++] = NS_AVG_P;
+    if (second) {
+        co_of[nco++] = NS_AVG_UU; co_of[nco++] = NS_AVG_VV; co_of[nco++] = NS_AVG_UV;
+        if (has_t) { co_of[nco++] = NS_AVG_TT; co_of[nco++] = NS_AVG_UT; co_of[nco++] = NS_AVG_VT; }
+        if (has_p) co_of[nco++] = NS_AVG_PP;
+    }
+    const size_t pl = (size_t)g.nxl * g.ld;
+    q.nplanes = (size_t)nsrc + nco;
+    int rc = dev_alloc(s, &q.mem, (q.nplanes + (has_p ? 1 : 0)) * pl * sizeof(double), true, "flow statistics planes");
+    if (!rc && has_p) rc = dev_alloc(s, &q.ppart, (size_t)nsg::derived_partials(g) * 9 * sizeof(double), false, "flow statistics partials");
+    if (rc) {
+        for (double** p : {&q.mem, &q.ppart}) {
+            if (*p) (void)hipFree(*p);
+            *p = nullptr;
+        }
+        return rc;
+    }
+    q.a = nsg::MomArgs{};
+    for (auto& p : q.plane) p = nullptr;
+    double* next = q.mem;
+    for (int k = 0; k < nsrc; k++, next += pl) q.plane[mean_of[k]] = q.a.mean[k] = next;
+    for (int k = 0; k < nco; k++, next += pl) q.plane[co_of[k]] = q.a.S[k] = next;
+    q.P = has_p ? next : nullptr;
+    q.a.nxl = g.nxl;
+    q.a.ny = g.ny;
+    q.a.ld = g.ld;
+    q.every = d->every;
+    q.flags = d->flags;
+    q.nsrc = nsrc;
+    q.n = q.steps = 0;
+    q.acc = ns_avg_stats{};
+    q.on = true;
+    return 0;
+}
+
+int ns_avg_reset(ns_solver* s) {
+    CHK(avg_on(s, "ns_avg_reset"));
+    HIPCHK(hipSetDevice(s->device));
+    auto& q = s->av;
+    HIPCHK(hipMemsetAsync(q.mem, 0, q.nplanes * (size_t)s->g.nxl * s->g.ld * sizeof(double), s->st));
+    q.n = q.steps = 0;
+    (void)s->tm.drain(nsg::tbit(nsg::T_AVG), nullptr);
+    q.acc = ns_avg_stats{};
+    return 0;
+}
+
+int ns_avg_sample(ns_solver* s) {
+    CHK(avg_on(s, "ns_avg_sample"));
+    CHK(materialize(s));
+    HIPCHK(hipSetDevice(s->device));
+    nsg::set_compute_cus(s->compute_cus);
+    return avg_sample(s);
+}
+
+int ns_avg_get(ns_solver* s, int which, double* plane) {
+    CHK(avg_on(s, "ns_avg_get"));
+    if (which < 0 || which >= NS_AVG_NUM) { set_err("ns_avg_get: unknown plane %d", which); return NS_EINVAL; }
+    auto& q = s->av;
+    if (!q.plane[which]) {
+        set_err("ns_avg_get: plane %d is not accumulated by this solver (ns_avg_enable's flags 0x%x)", which, (unsigned)q.flags);
+        return NS_EINVAL;
+    }
+    if (!plane) { set_err("ns_avg_get: the output plane is NULL"); return NS_EINVAL; }
+    HIPCHK(hipSetDevice(s->device));
+    const nsg::Geo& g = s->g;
+    const size_t cells = (size_t)g.nxl * g.ny;
+    if (q.n == 0) {   // (nothing sampled: every plane is 0, and there is no 1 / n)
+        HIPCHK(hipStreamSynchronize(s->st));
+        std::fill(plane, plane + cells, 0.0);
+        return 0;
+    }
+    HIPCHK(hipMemcpy2DAsync(plane, (size_t)g.ny * 8, q.plane[which], (size_t)g.ld * 8, (size_t)g.ny * 8, g.nxl,
+                            hipMemcpyDeviceToHost, s->st));
+    HIPCHK(hipStreamSynchronize(s->st));
+    if (which >= NS_AVG_UU) {   // the population covariance S / n: one multiplication by the host-formed 1 / n
+        const double rn = 1.0 / (double)q.n;
+        for (size_t k = 0; k < cells; k++) plane[k] *= rn;
+    }
+    return 0;
+}
+
+int ns_avg_last(ns_solver* s, ns_avg_stats* out) {
+    CHK(avg_on(s, "ns_avg_last"));
+    if (!out) { set_err("ns_avg_last: out is NULL"); return NS_EINVAL; }
+    HIPCHK(hipSetDevice(s->device));
+    auto& q = s->av;
+    HIPCHK(hipStreamSynchronize(s->st));
+    TCHK(s->tm.drain(nsg::tbit(nsg::T_AVG), nullptr, nullptr, nullptr, nullptr, &q.acc));
+    ns_avg_stats r = q.acc;
+    q.acc = ns_avg_stats{};
+    r.n = q.n;
+    r.steps = q.steps;
     *out = r;
     return 0;
 }

@@ -25,6 +25,7 @@ struct Options {
     bool do_export = true;
     bool derived = false;   // -derived: Derived_<iter>.csv beside every export, one summary line after the last step
     std::string tracers;    // -tracers seeds.csv: particles carried by the step, Tracers_<iter>.csv beside every export
+    int averages = 0;       // -averages N: running means and Reynolds stresses of u, v, P every N steps, Averages.csv after the last
 };
 Options g_opt;
 
@@ -52,6 +53,8 @@ PetscErrorCode PetscInitialize(int* argc, char*** argv, const char*, const char*
             g_opt.derived = true;
         } else if (!std::strcmp(a, "-tracers")) {
             g_opt.tracers = next();
+        } else if (!std::strcmp(a, "-averages")) {
+            g_opt.averages = std::atoi(next());
         } else {
             keep.push_back((*argv)[k]);  // positional arguments (grid file, sim file) stay
         }
@@ -297,6 +300,34 @@ void write_tracers_csv(int iter, ns_solver* gpu, int64_t n, double ox, double oy
     std::fclose(f);
 }
 
+// -averages: the running statistics after the last step (ns_avg_get), one line per domain cell in FlowData's cell
+// order: the cell centre, the means and the population covariances
+void write_averages_csv(ns_solver* gpu, Grid& g) {
+    const int nx = g.nxCells(), ny = g.nyCells();
+    static const int which[] = {NS_AVG_U, NS_AVG_V, NS_AVG_P, NS_AVG_UU, NS_AVG_VV, NS_AVG_UV, NS_AVG_PP};
+    constexpr int NW = sizeof which / sizeof which[0];
+    vector<double> pl[NW];
+    for (int k = 0; k < NW; k++) {
+        pl[k].resize((size_t)nx * ny);
+        if (ns_avg_get(gpu, which[k], pl[k].data()) != 0) {
+            cout << "Averages failed: " << ns_last_error() << "\n";
+            return;
+        }
+    }
+    FILE* f = std::fopen("Averages.csv", "w");
+    if (!f) return;
+    std::fprintf(f, "Point_X,Point_Y,U_mean,V_mean,Pr_mean,uu,vv,uv,pp\n");
+    for (int i = 0; i < nx; i++)
+        for (int j = 0; j < ny; j++) {
+            if (!g.inDomain(i, j)) continue;
+            const size_t c = (size_t)i * ny + j;
+            std::fprintf(f, "%.15g,%.15g", g.centerX(i), g.centerY(j));
+            for (int k = 0; k < NW; k++) std::fprintf(f, ",%.17g", pl[k][c]);
+            std::fprintf(f, "\n");
+        }
+    std::fclose(f);
+}
+
 }  // namespace
 
 void FluidSolver::Solve() {
@@ -318,6 +349,12 @@ void FluidSolver::Solve() {
                 ntr = (int64_t)sx.size();
             else cout << "Tracers failed: " << ns_last_error() << "\n";
         }
+    }
+    bool avg = false;           // -averages: enabled (false: not asked for, or the option failed)
+    if (g_opt.averages != 0) {
+        const ns_avg_desc ad{g_opt.averages, NS_AVG_SECOND | NS_AVG_PRESSURE};   // (no scalar in this driver: no T)
+        if (ns_avg_enable(m.gpu, &ad) == 0) avg = true;
+        else cout << "Averages failed: " << ns_last_error() << "\n";
     }
     int iter = 1;
     do {
@@ -357,6 +394,13 @@ void FluidSolver::Solve() {
             printf("tracers: n %lld live %lld exited %lld stuck %lld age_max %.9e\n", (long long)ts.n, (long long)ts.live,
                    (long long)ts.exited, (long long)ts.stuck, ts.age_max);
         else cout << "Tracers failed: " << ns_last_error() << "\n";
+    }
+    if (avg) {
+        ns_avg_stats as{};
+        if (ns_avg_last(m.gpu, &as) == 0) {
+            write_averages_csv(m.gpu, *grid);
+            printf("averages: n=%lld steps=%lld\n", (long long)as.n, (long long)as.steps);
+        } else cout << "Averages failed: " << ns_last_error() << "\n";
     }
     fflush(stdout);
     cout << "Solution Complete!\n";

@@ -252,6 +252,67 @@ class GpuSolver:
         L.check(L.lib().ns_tracers_reset(self._h))
         self._tracers = 0
 
+    # ---- running flow statistics (ns_avg_*: one rank)
+    _AVG_KEYS = ("u", "v", "p", "T", "uu", "vv", "uv", "pp", "TT", "uT", "vT")   # NS_AVG_U .. NS_AVG_VT
+
+    def enable_averages(self, every: int = 1, second: bool = True, pressure: bool = False, scalar: bool = False) -> None:
+        """Running means of u, v (pressure: and P, scalar: and T -- after enable_scalar) and, with second, the
+        Reynolds stresses uu, vv, uv (and pp / TT, uT, vT), accumulated on the device: step k since here (or
+        reset_averages) with k % every == 0 samples the state it starts from.  Once per solver.  Pressure
+        statistics cost one extra derived-field pass per sample."""
+        flags = ((L.NS_AVG_SECOND if second else 0) | (L.NS_AVG_PRESSURE if pressure else 0) |
+                 (L.NS_AVG_SCALAR if scalar else 0))
+        self.enable_averages_flags(every, flags)
+
+    def enable_averages_flags(self, every: int, flags: int) -> None:
+        """ns_avg_enable with the raw NS_AVG_* flag bits."""
+        desc = L.NsAvgDesc(int(every), int(flags))
+        L.check(L.lib().ns_avg_enable(self._h, ctypes.byref(desc)))
+        self._avg_flags = int(flags)
+
+    def sample_averages(self) -> None:
+        """One sample of the current fields between steps (how a caller adds the final state)."""
+        L.check(L.lib().ns_avg_sample(self._h))
+
+    def reset_averages(self) -> None:
+        """n = 0, steps = 0, every plane zero: the spin-up cut-off."""
+        L.check(L.lib().ns_avg_reset(self._h))
+        self._avg_kept = (0.0, 0)
+
+    def average_plane(self, which: int) -> np.ndarray:
+        out = np.empty(self.shape, dtype=np.float64)
+        L.check(L.lib().ns_avg_get(self._h, int(which), _dptr(out)))
+        return out
+
+    def averages(self) -> dict:
+        """The planes accumulated, as (nx, ny) arrays (0 outside a polygon) under the keys u, v, p, T (the means)
+        and uu, vv, uv, pp, TT, uT, vT (the population covariances), plus n, the number of samples."""
+        f = getattr(self, "_avg_flags", None)
+        if f is None:
+            L.check(L.lib().ns_avg_get(self._h, L.NS_AVG_U, None))   # (raises: not enabled)
+        sec, pr, sc = f & L.NS_AVG_SECOND, f & L.NS_AVG_PRESSURE, f & L.NS_AVG_SCALAR
+        have = {"u": True, "v": True, "p": pr, "T": sc, "uu": sec, "vv": sec, "uv": sec, "pp": sec and pr,
+                "TT": sec and sc, "uT": sec and sc, "vT": sec and sc}
+        n = self._average_counts()[0]
+        out = {k: self.average_plane(i) for i, k in enumerate(self._AVG_KEYS) if have[k]}
+        out["n"] = n
+        return out
+
+    def _average_counts(self):
+        # (n and steps without ns_avg_last, which hands the kernel time out once: kept for average_stats)
+        st = L.NsAvgStats()
+        L.check(L.lib().ns_avg_last(self._h, ctypes.byref(st)))
+        keep = getattr(self, "_avg_kept", (0.0, 0))
+        self._avg_kept = (keep[0] + st.t_kernel_ms, keep[1] + st.n_kernels)
+        return st.n, st.steps
+
+    def average_stats(self) -> dict:
+        """n, steps since enable / reset and the sample passes' kernel time since the last call (timing on)."""
+        n, steps = self._average_counts()
+        t, k = self._avg_kept
+        self._avg_kept = (0.0, 0)
+        return {"n": n, "steps": steps, "t_kernel_ms": t, "n_kernels": k}
+
     # ---- passive scalar (ns_scalar_*: one rank's rectangle)
     def enable_scalar(self, pe: float, bc) -> None:
         """A scalar T carried by the step, Peclet number pe.  bc: one ("dirichlet", value) or ("zerograd",)
