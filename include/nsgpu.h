@@ -461,6 +461,67 @@ int  ns_avg_sample(ns_solver* s);
 int  ns_avg_get(ns_solver* s, int which, double* plane);
 int  ns_avg_last(ns_solver* s, ns_avg_stats* out);
 
+/* ---- wall loads: pressure, shear and heat flux per boundary edge, on the device ----
+ * The scheme's own boundary fluxes on every boundary face of the domain and their sums per edge ("Wall
+ * loads"; the normative statement is tests/loads_ref.py).  A boundary face is face k (0 W, 1 E, 2 S, 3 N) of a domain
+ * cell whose neighbour there is not in the domain; it belongs to the grid edge e that ns_edge_profile and ns_scalar_bc
+ * index by.  n = the face's outward normal, h the cell's spacing along n, ds the other one, s the face centre's
+ * coordinate along the edge from the box's lower-left corner.  Per face:
+ *   p   ns_derive's pressure P of the adjacent cell, on every face type (first order on a NEUMANN face: nothing is
+ *       extrapolated to the face)
+ *   tx  (ghost(u) - u) / (re h), ty likewise with v: the diffusive momentum flux the scheme passes through the face,
+ *       the traction on the fluid; the ghost is the step's own velocity ghost, an edge profile's entry included
+ *   un  face(u) n_x + face(v) n_y with the divergence's face values 0.5 (q + ghost)
+ *   tb  0.5 (T + ghost(T)), qn = -(ghost(T) - T) / (pe h): the scalar on the face and the conductive heat flux leaving
+ *       the fluid; ghost(T) = T on a zero-gradient edge, -T + 2 value on a Dirichlet one.  Exactly 0 without a scalar
+ * Per edge the NS_LOAD_NUM sums over its faces, below.  The force of the fluid on the wall is (fpx + fvx, fpy + fvy).
+ * The sums are reproducible bit for bit: their order is a function of the face list alone (no floating-point atomics).
+ *   in the step:     step k since enable / reset (k = 0, 1, ..) with k % every == 0 appends one record -- k and the
+ *                    n_edges x NS_LOAD_NUM sums of the state the step starts from, u^n, v^n, phi^n, T^n -- to a device
+ *                    ring of `capacity` records, right behind K1, in ns_step and ns_step_async alike; a full ring
+ *                    overwrites its oldest record.  No host sync, wait or readback is added
+ *   ns_loads_sample: appends a record of the current fields between steps, its step -1 (a deferred correction is
+ *                    settled first, as by ns_get_array)
+ *   ns_loads_edges:  the current fields' n_edges x NS_LOAD_NUM sums; no record; synchronises
+ *   ns_loads_faces:  the current fields' per-face arrays of one edge in ascending s, ns_loads_face_count entries each;
+ *                    any pointer may be NULL; synchronises
+ *   ns_loads_history: records [first, first + n) of those held, oldest first: step[n], rec[n][n_edges][NS_LOAD_NUM]
+ *                    (either may be NULL); synchronises
+ *   ns_loads_reset:  total = held = steps = 0
+ *   ns_loads_last:   the counters and the sampling kernels' time since the last call (timing == 1; two launches per
+ *                    sample); synchronises
+ * A solver that never enables them runs exactly the launches it ran before.  The buffers are allocated by
+ * ns_loads_enable (not counted by ns_device_bytes).  The scalar columns exist wherever a scalar does.
+ * NS_EINVAL (the message names the cause): a null solver or descriptor, every < 1, capacity < 1, enabling twice, any
+ * other ns_loads_* call before ns_loads_enable, a bad edge index, a history range outside [0, held), nranks > 1 (P is
+ * the one-rank derived pass's).  Additive to ABI 9. */
+#define NS_LOAD_LEN      0   /* sum ds */
+#define NS_LOAD_FPX      1   /* sum p n_x ds */
+#define NS_LOAD_FPY      2
+#define NS_LOAD_FVX      3   /* -sum tx ds */
+#define NS_LOAD_FVY      4
+#define NS_LOAD_Q        5   /* sum un ds: the flow rate out of the domain */
+#define NS_LOAD_HEAT     6   /* sum qn ds */
+#define NS_LOAD_HEAT_ADV 7   /* sum un tb ds */
+#define NS_LOAD_NUM      8
+typedef struct ns_load_desc  { int32_t every; int32_t capacity; } ns_load_desc;
+typedef struct ns_load_faces { double *s, *ds, *p, *tx, *ty, *un, *tb, *qn; } ns_load_faces;
+typedef struct ns_load_stats {
+    int64_t total;               /* samples taken since enable / reset */
+    int64_t held;                /* records in the ring: min(total, capacity) */
+    int64_t steps;               /* steps since enable / reset */
+    double  t_kernel_ms;         /* the sampling kernels since the last ns_loads_last (timing == 1) */
+    int32_t n_kernels;           /* two per sample: the face kernel and the edge sums */
+} ns_load_stats;
+int  ns_loads_enable(ns_solver* s, const ns_load_desc* d);   /* once per solver */
+int  ns_loads_sample(ns_solver* s);
+int  ns_loads_edges(ns_solver* s, double* out);
+int  ns_loads_face_count(ns_solver* s, int32_t edge, int64_t* n);
+int  ns_loads_faces(ns_solver* s, int32_t edge, const ns_load_faces* out);
+int  ns_loads_history(ns_solver* s, int64_t first, int64_t n, int64_t* step, double* rec);
+int  ns_loads_reset(ns_solver* s);
+int  ns_loads_last(ns_solver* s, ns_load_stats* out);
+
 /* ---- host-side helpers (no GPU needed) ---- */
 /* the face averages of the parabola 6 s (1 - s) * mean over the faces k0 <= k < k1 of spacings h[0..n) (s runs 0..1
  * from face k0's lower end to face k1-1's upper end), 0 elsewhere: the average over [sa, sb] is

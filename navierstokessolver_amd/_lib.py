@@ -150,6 +150,26 @@ class NsAvgStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+(NS_LOAD_LEN, NS_LOAD_FPX, NS_LOAD_FPY, NS_LOAD_FVX, NS_LOAD_FVY, NS_LOAD_Q, NS_LOAD_HEAT, NS_LOAD_HEAT_ADV) = range(8)
+NS_LOAD_NUM = 8
+
+
+class NsLoadDesc(ctypes.Structure):
+    _fields_ = [("every", ctypes.c_int32), ("capacity", ctypes.c_int32)]
+
+
+class NsLoadFaces(ctypes.Structure):
+    _fields_ = [(k, ctypes.POINTER(ctypes.c_double)) for k in ("s", "ds", "p", "tx", "ty", "un", "tb", "qn")]
+
+
+class NsLoadStats(ctypes.Structure):
+    _fields_ = [("total", ctypes.c_int64), ("held", ctypes.c_int64), ("steps", ctypes.c_int64),
+                ("t_kernel_ms", ctypes.c_double), ("n_kernels", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _P = ctypes.c_void_p
 _D = ctypes.POINTER(ctypes.c_double)
 SIGNATURES = {
@@ -190,6 +210,14 @@ SIGNATURES = {
     "ns_avg_sample": (ctypes.c_int, [_P]),
     "ns_avg_get": (ctypes.c_int, [_P, ctypes.c_int, _D]),
     "ns_avg_last": (ctypes.c_int, [_P, ctypes.POINTER(NsAvgStats)]),
+    "ns_loads_enable": (ctypes.c_int, [_P, ctypes.POINTER(NsLoadDesc)]),
+    "ns_loads_sample": (ctypes.c_int, [_P]),
+    "ns_loads_edges": (ctypes.c_int, [_P, _D]),
+    "ns_loads_face_count": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]),
+    "ns_loads_faces": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.POINTER(NsLoadFaces)]),
+    "ns_loads_history": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), _D]),
+    "ns_loads_reset": (ctypes.c_int, [_P]),
+    "ns_loads_last": (ctypes.c_int, [_P, ctypes.POINTER(NsLoadStats)]),
     "ns_parabolic_profile": (ctypes.c_int, [_D, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, _D]),
     "ns_slab_range": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                      ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),

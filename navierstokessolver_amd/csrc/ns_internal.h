@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "ns_knobs.h"
+#include "ns_loads_host.h"
 
 #ifndef NS_TAILS
 #define NS_TAILS 1   // (r7) 0: K1''s reduction and the direct solve's group scans keep their own launches (A/B: make
@@ -186,6 +187,28 @@ struct MomArgs {
 };
 // k_moments<NSRC, SECOND, HAS_T>; -1: no such instantiation, or a plane not 16-byte aligned
 int launch_moments(const MomArgs& A, int nsrc, bool second, bool has_t, hipStream_t st);
+// wall loads (ns_loads_*; DESIGN.md 4, "Wall loads"; ns_loads.hip; the normative statement is tests/loads_ref.py): the
+// scheme's own boundary fluxes per boundary face and their sums per edge, from the planes u, v, phi (and T: null
+// without a scalar, whose ghost across rectangle side k is tneu[k] ? T : -T + tc[k]).  face / chunk / cs: the device
+// copies of ns_loads_host.h's list (nf faces, nchunk chunks, n_edges + 1 chunk offsets).  val: 6 planes of nf doubles
+// -- p, tx, ty, un, tb, qn per face; part: 8 doubles per chunk, the chunk's partial of each of the NS_LOAD_NUM sums
+struct LoadArgs {
+    Geo g;
+    Coef c;
+    double alpha, re, pe;   // dt / (2 re): the pressure's; the Reynolds and the Peclet number
+    const double *u, *v, *phi, *T;
+    int tneu[4];
+    double tc[4];
+    const LoadFace* face;
+    const LoadChunk* chunk;
+    const int32_t* cs;
+    double *val, *part;
+    int nf, nchunk, n_edges;
+};
+// k_load_faces<Topo>: one workgroup per chunk, one thread per face; -1: refused (slabs, an empty list)
+int launch_load_faces(const LoadArgs& A, hipStream_t st);
+// k_load_edges: out[8 e + q] = the partials of edge e's chunks added in ascending order
+int launch_load_edges(const LoadArgs& A, double* out, hipStream_t st);
 // K2: fused red-black SOR sweep of (I - a L_V) on u and v, (u,v) -> (uo,vo);
 //     residual^2 partials of the input if part != null: u at part[0..n), v at part[n..2n), n returned
 int launch_helm_sweep(const Knobs& kn, const Geo& g, const Coef& c, double alpha, double omega, const double* u, const double* v,

@@ -429,6 +429,21 @@ struct ns_solver {
         nsg::MomArgs a{};
         ns_avg_stats acc{};      // the drained sample intervals nobody has asked for yet
     } av;
+    // wall loads (ns_loads_enable; DESIGN.md 4 "Wall loads"): nothing below exists without them.  list: the host's
+    // boundary-face list (its s and ds tables are handed out from here); tab: its device copy (faces | chunks | chunk
+    // offsets); val: the faces' six values; part: the chunks' partials; ring: capacity + 1 records of nrec doubles, the
+    // last one ns_loads_edges' own.  The ring's counters and step numbers live on the host: slot = sample % capacity
+    struct Loads {
+        bool on = false;
+        int every = 1, capacity = 0, nrec = 0;
+        int64_t total = 0, steps = 0;
+        nsg::LoadList list;
+        int32_t* tab = nullptr;
+        double *val = nullptr, *part = nullptr, *ring = nullptr;
+        std::vector<int64_t> rstep;
+        nsg::LoadArgs a{};
+        ns_load_stats acc{};     // the drained sample intervals nobody has asked for yet
+    } lo;
 };
 
 namespace {
@@ -3404,6 +3419,50 @@ int avg_sample(ns_solver* s) {
     return 0;
 }
 
+// ---------------- wall loads (ns_loads_enable; DESIGN.md 4 "Wall loads")
+// the boundary faces' values and the edges' sums of the planes U, V, PHI (T) hold now, on the solver's stream: the face
+// kernel, then (out != null) the edge sums into the record at out.  The geometry and the scalar's state are read per
+// launch: an edge profile or a scalar enabled since the last one changes them.  No sync, no readback
+int loads_run(ns_solver* s, double* out, bool timed) {
+    auto& q = s->lo;
+    nsg::LoadArgs& a = q.a;
+    a.g = s->g;
+    a.c = s->c;
+    a.alpha = s->dt / (2 * s->re);
+    a.re = s->re;
+    a.u = s->arr[NS_ARR_U];
+    a.v = s->arr[NS_ARR_V];
+    a.phi = s->arr[NS_ARR_PHI];
+    a.T = s->sc.on ? s->sc.T : nullptr;   // (the scalar's current plane: its sweeps swap T and its partner)
+    a.pe = s->sc.on ? s->sc.pe : 1.0;
+    for (int k = 0; k < 4; k++) {
+        a.tneu[k] = s->sc.neu[k];
+        a.tc[k] = s->sc.c[k];
+    }
+    {
+        Timing::Scope iv;
+        TCHK(s->tm.open(iv, nsg::T_LOADS, timed && s->timing));
+        if (nsg::launch_load_faces(a, s->st) < 0) { set_err("wall loads: the face kernel's launch was refused"); return NS_EHIP; }
+        TCHK(iv.close());
+    }
+    if (out) {
+        Timing::Scope iv;
+        TCHK(s->tm.open(iv, nsg::T_LOADS, timed && s->timing));
+        if (nsg::launch_load_edges(a, out, s->st) < 0) { set_err("wall loads: the edge sums' launch was refused"); return NS_EHIP; }
+        TCHK(iv.close());
+    }
+    return 0;
+}
+// one record appended to the ring: `step` and the sums of the current planes
+int loads_sample(ns_solver* s, int64_t step) {
+    auto& q = s->lo;
+    const int64_t slot = q.total % q.capacity;
+    CHK(loads_run(s, q.ring + (size_t)slot * q.nrec, true));
+    q.rstep[slot] = step;
+    q.total++;
+    return 0;
+}
+
 int check_arr(ns_solver* s, int which) {
     if (!s) { set_err("null solver"); return NS_EINVAL; }
     if (which < 0 || which >= NS_NUM_ARR) { set_err("bad array index %d", which); return NS_EINVAL; }
@@ -4230,6 +4289,9 @@ void ns_destroy(ns_solver* s) {
     if (s->tr.hs) (void)hipHostFree(s->tr.hs);
     for (double* q : {s->av.mem, s->av.ppart})
         if (q) (void)hipFree(q);
+    for (double* q : {s->lo.val, s->lo.part, s->lo.ring})
+        if (q) (void)hipFree(q);
+    if (s->lo.tab) (void)hipFree(s->lo.tab);
     if (s->comm) (void)ncclCommDestroy(s->comm);
     if (s->mev) (void)hipEventDestroy(s->mev);
     if (s->mm_host) (void)hipHostFree(s->mm_host);
@@ -4295,7 +4357,7 @@ static int step_body(ns_solver* s, ns_stats& st) {
 static int step_body_(ns_solver* s, ns_stats& st) {
     // (intervals a standalone kernel call or a failed step left behind are dropped; K5's wait for their drain below)
     // (the flow statistics' intervals are kept: they add up until ns_avg_last asks)
-    (void)s->tm.drain(~(nsg::tbit(nsg::T_K5) | nsg::tbit(nsg::T_AVG)), nullptr);
+    (void)s->tm.drain(~(nsg::tbit(nsg::T_K5) | nsg::tbit(nsg::T_AVG) | nsg::tbit(nsg::T_LOADS)), nullptr);
     CHK(rhs(s, true));                                             // ConstructRHS_V       (:546)
     // the flow statistics sample the state the step starts from -- u^n, v^n, phi^n, T^n -- directly behind K1 (after
     // it U, V hold u^n, v^n in the deferred-K5 path too), ahead of the scalar's first batch, which swaps T^n away,
@@ -4303,6 +4365,11 @@ static int step_body_(ns_solver* s, ns_stats& st) {
     if (s->av.on) {
         if (s->av.steps % s->av.every == 0) CHK(avg_sample(s));
         s->av.steps++;
+    }
+    // ... and so do the wall loads: one record of the boundary fluxes of u^n, v^n, phi^n, T^n
+    if (s->lo.on) {
+        if (s->lo.steps % s->lo.every == 0) CHK(loads_sample(s, s->lo.steps));
+        s->lo.steps++;
     }
     // the passive scalar sees u^n, v^n as K1 does (which wrote them in the deferred-K5 path): its right-hand side
     // and first batch of sweeps here, their residual read after the velocities' Helmholtz check
@@ -4327,6 +4394,7 @@ static int step_body_(ns_solver* s, ns_stats& st) {
     // B/cell --, K1, the wall bands and the previous step's K5)
     TCHK(s->tm.drain(nsg::tbit(nsg::T_HELM) | nsg::tbit(nsg::T_K1) | nsg::tbit(nsg::T_BAND) | nsg::tbit(nsg::T_K5), &st));
     if (s->av.on) TCHK(s->tm.drain(nsg::tbit(nsg::T_AVG), nullptr, nullptr, nullptr, nullptr, &s->av.acc));
+    if (s->lo.on) TCHK(s->tm.drain(nsg::tbit(nsg::T_LOADS), nullptr, nullptr, nullptr, nullptr, nullptr, &s->lo.acc));
     if (!s->k3_spec) CHK(divergence(s));                           // ConstructRHS_phi + mean (:549-550)
     s->k3_spec = 0;
     CHK(consistent_rhs(s));                                        // stretched grids only
@@ -4885,6 +4953,184 @@ int ns_avg_last(ns_solver* s, ns_avg_stats* out) {
     ns_avg_stats r = q.acc;
     q.acc = ns_avg_stats{};
     r.n = q.n;
+    r.steps = q.steps;
+    *out = r;
+    return 0;
+}
+
+// ---------------- wall loads ("Wall loads"): the entry points.  One rank; buffers of their own
+static int loads_on(ns_solver* s, const char* who) {
+    if (!s) { set_err("null solver"); return NS_EINVAL; }
+    if (!s->lo.on) { set_err("%s: wall loads are not enabled (ns_loads_enable)", who); return NS_EINVAL; }
+    return 0;
+}
+static int loads_edge(ns_solver* s, const char* who, int32_t edge) {
+    CHK(loads_on(s, who));
+    if (edge < 0 || edge >= s->n_edges) { set_err("%s: edge %d of a grid with %d edges", who, edge, s->n_edges); return NS_EINVAL; }
+    return 0;
+}
+
+int ns_loads_enable(ns_solver* s, const ns_load_desc* d) {
+    if (!s) { set_err("null solver"); return NS_EINVAL; }
+    if (!d) { set_err("ns_loads_enable: the descriptor is NULL"); return NS_EINVAL; }
+    if (s->lo.on) { set_err("ns_loads_enable: wall loads are already enabled"); return NS_EINVAL; }
+    if (d->every < 1) { set_err("ns_loads_enable: every = %d is less than 1", d->every); return NS_EINVAL; }
+    if (d->capacity < 1) { set_err("ns_loads_enable: capacity = %d is less than 1", d->capacity); return NS_EINVAL; }
+    if (s->nranks > 1) { set_err("ns_loads_enable: nranks > 1 is not supported (the pressure comes from ns_derive, one rank)"); return NS_EINVAL; }
+    HIPCHK(hipSetDevice(s->device));
+    auto& q = s->lo;
+    const nsg::Geo& g = s->g;
+    std::vector<double> hx(g.nx), hy(g.ny);
+    HIPCHK(hipMemcpy(hx.data(), s->c.hx, (size_t)g.nx * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(hy.data(), s->c.hy, (size_t)g.ny * sizeof(double), hipMemcpyDeviceToHost));
+    // the topology as the kernels see it: a rectangle's sides, or the masked domain's code plane
+    std::vector<int32_t> fc;
+    if (g.fc) {
+        fc.resize((size_t)g.nxl * g.ld);
+        HIPCHK(hipMemcpy(fc.data(), g.fc, fc.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    auto inside = [&](int i, int j) { return fc.empty() || (fc[(size_t)i * g.ld + j] & nsg::FC_IN) != 0; };
+    auto edge_of = [&](int i, int j, int k) {
+        if (fc.empty()) {
+            const bool bnd = k == 0 ? i == 0 : k == 1 ? i == g.nx - 1 : k == 2 ? j == 0 : j == g.ny - 1;
+            return bnd ? s->side_edge[k] : -1;
+        }
+        const int e = nsg::fc_edge(fc[(size_t)i * g.ld + j], k);
+        return e == nsg::FC_INT ? -1 : e;
+    };
+    nsg::LoadList L;
+    if (!nsg::build_load_list(g.nx, g.ny, g.ld, s->n_edges, hx.data(), hy.data(), inside, edge_of, L) || L.face.empty()) {
+        set_err("ns_loads_enable: the boundary-face list could not be built");
+        return NS_EINVAL;
+    }
+    const size_t nf = L.face.size(), nch = L.chunk.size(), nrec = (size_t)s->n_edges * NS_LOAD_NUM;
+    // one table block: faces | chunks (16 bytes each) | the edges' chunk offsets
+    std::vector<int32_t> tab(4 * (nf + nch) + L.cs.size());
+    std::memcpy(tab.data(), L.face.data(), nf * sizeof(nsg::LoadFace));
+    std::memcpy(tab.data() + 4 * nf, L.chunk.data(), nch * sizeof(nsg::LoadChunk));
+    std::memcpy(tab.data() + 4 * (nf + nch), L.cs.data(), L.cs.size() * sizeof(int32_t));
+    int rc = dev_upload(s, &q.tab, tab, "wall-load tables");
+    if (!rc) rc = dev_alloc(s, &q.val, 6 * nf * sizeof(double), true, "wall-load face values");
+    if (!rc) rc = dev_alloc(s, &q.part, nch * NS_LOAD_NUM * sizeof(double), true, "wall-load partials");
+    if (!rc) rc = dev_alloc(s, &q.ring, ((size_t)d->capacity + 1) * nrec * sizeof(double), true, "wall-load records");
+    if (rc) {
+        for (double** p : {&q.val, &q.part, &q.ring}) {
+            if (*p) (void)hipFree(*p);
+            *p = nullptr;
+        }
+        if (q.tab) (void)hipFree(q.tab);
+        q.tab = nullptr;
+        return rc;
+    }
+    q.a = nsg::LoadArgs{};
+    q.a.face = reinterpret_cast<const nsg::LoadFace*>(q.tab);
+    q.a.chunk = reinterpret_cast<const nsg::LoadChunk*>(q.tab + 4 * nf);
+    q.a.cs = q.tab + 4 * (nf + nch);
+    q.a.val = q.val;
+    q.a.part = q.part;
+    q.a.nf = (int)nf;
+    q.a.nchunk = (int)nch;
+    q.a.n_edges = s->n_edges;
+    q.list = std::move(L);
+    q.every = d->every;
+    q.capacity = d->capacity;
+    q.nrec = (int)nrec;
+    q.rstep.assign((size_t)d->capacity, 0);
+    q.total = q.steps = 0;
+    q.acc = ns_load_stats{};
+    q.on = true;
+    return 0;
+}
+
+int ns_loads_reset(ns_solver* s) {
+    CHK(loads_on(s, "ns_loads_reset"));
+    auto& q = s->lo;
+    q.total = q.steps = 0;
+    (void)s->tm.drain(nsg::tbit(nsg::T_LOADS), nullptr);
+    q.acc = ns_load_stats{};
+    return 0;
+}
+
+int ns_loads_sample(ns_solver* s) {
+    CHK(loads_on(s, "ns_loads_sample"));
+    CHK(materialize(s));
+    HIPCHK(hipSetDevice(s->device));
+    nsg::set_compute_cus(s->compute_cus);
+    return loads_sample(s, -1);
+}
+
+int ns_loads_edges(ns_solver* s, double* out) {
+    CHK(loads_on(s, "ns_loads_edges"));
+    if (!out) { set_err("ns_loads_edges: out is NULL"); return NS_EINVAL; }
+    CHK(materialize(s));
+    HIPCHK(hipSetDevice(s->device));
+    nsg::set_compute_cus(s->compute_cus);
+    auto& q = s->lo;
+    double* rec = q.ring + (size_t)q.capacity * q.nrec;   // (the record behind the ring)
+    CHK(loads_run(s, rec, false));
+    HIPCHK(hipMemcpyAsync(out, rec, (size_t)q.nrec * sizeof(double), hipMemcpyDeviceToHost, s->st));
+    HIPCHK(hipStreamSynchronize(s->st));
+    return 0;
+}
+
+int ns_loads_face_count(ns_solver* s, int32_t edge, int64_t* n) {
+    CHK(loads_edge(s, "ns_loads_face_count", edge));
+    if (!n) { set_err("ns_loads_face_count: n is NULL"); return NS_EINVAL; }
+    *n = s->lo.list.fs[edge + 1] - s->lo.list.fs[edge];
+    return 0;
+}
+
+int ns_loads_faces(ns_solver* s, int32_t edge, const ns_load_faces* out) {
+    CHK(loads_edge(s, "ns_loads_faces", edge));
+    if (!out) { set_err("ns_loads_faces: out is NULL"); return NS_EINVAL; }
+    CHK(materialize(s));
+    HIPCHK(hipSetDevice(s->device));
+    nsg::set_compute_cus(s->compute_cus);
+    auto& q = s->lo;
+    const size_t f0 = (size_t)q.list.fs[edge], n = (size_t)q.list.fs[edge + 1] - f0, nf = q.list.face.size();
+    if (out->s) std::copy(q.list.s.begin() + f0, q.list.s.begin() + f0 + n, out->s);
+    if (out->ds) std::copy(q.list.ds.begin() + f0, q.list.ds.begin() + f0 + n, out->ds);
+    double* const dst[6] = {out->p, out->tx, out->ty, out->un, out->tb, out->qn};
+    if (n == 0 || std::all_of(dst, dst + 6, [](double* p) { return !p; })) return 0;
+    CHK(loads_run(s, nullptr, false));
+    for (int k = 0; k < 6; k++)
+        if (dst[k]) HIPCHK(hipMemcpyAsync(dst[k], q.val + k * nf + f0, n * sizeof(double), hipMemcpyDeviceToHost, s->st));
+    HIPCHK(hipStreamSynchronize(s->st));
+    return 0;
+}
+
+int ns_loads_history(ns_solver* s, int64_t first, int64_t n, int64_t* step, double* rec) {
+    CHK(loads_on(s, "ns_loads_history"));
+    auto& q = s->lo;
+    const int64_t held = std::min<int64_t>(q.total, q.capacity);
+    if (first < 0 || n < 0 || first > held || n > held - first) {
+        set_err("ns_loads_history: the range [%lld, %lld) is outside [0, %lld)", (long long)first, (long long)(first + n), (long long)held);
+        return NS_EINVAL;
+    }
+    HIPCHK(hipSetDevice(s->device));
+    const int64_t oldest = q.total - held;   // (sample number of the oldest record held; its slot: % capacity)
+    for (int64_t k = 0; k < n; k++) {
+        const int64_t slot = (oldest + first + k) % q.capacity;
+        if (step) step[k] = q.rstep[slot];
+        if (rec)
+            HIPCHK(hipMemcpyAsync(rec + (size_t)k * q.nrec, q.ring + (size_t)slot * q.nrec, (size_t)q.nrec * sizeof(double),
+                                  hipMemcpyDeviceToHost, s->st));
+    }
+    HIPCHK(hipStreamSynchronize(s->st));
+    return 0;
+}
+
+int ns_loads_last(ns_solver* s, ns_load_stats* out) {
+    CHK(loads_on(s, "ns_loads_last"));
+    if (!out) { set_err("ns_loads_last: out is NULL"); return NS_EINVAL; }
+    HIPCHK(hipSetDevice(s->device));
+    auto& q = s->lo;
+    HIPCHK(hipStreamSynchronize(s->st));
+    TCHK(s->tm.drain(nsg::tbit(nsg::T_LOADS), nullptr, nullptr, nullptr, nullptr, nullptr, &q.acc));
+    ns_load_stats r = q.acc;
+    q.acc = ns_load_stats{};
+    r.total = q.total;
+    r.held = std::min<int64_t>(q.total, q.capacity);
     r.steps = q.steps;
     *out = r;
     return 0;

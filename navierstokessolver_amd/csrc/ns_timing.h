@@ -20,13 +20,13 @@ namespace nsg {
 
 // one kind per stats line; T_RAW has none (ns_time_poisson*: drain_raw)
 enum TKind : uint8_t { T_SWEEP, T_RESTRICT, T_CYCLE, T_GUESS, T_HELM, T_K1, T_BAND, T_K5, T_FPS_DCT, T_FPS_TRI,
-                       T_FPS_IDCT, T_SCALAR_RHS, T_DERIVED, T_TRACER, T_AVG, T_RAW, T_NKIND };
+                       T_FPS_IDCT, T_SCALAR_RHS, T_DERIVED, T_TRACER, T_AVG, T_LOADS, T_RAW, T_NKIND };
 constexpr unsigned tbit(TKind k) { return 1u << k; }
 constexpr unsigned T_MG = tbit(T_SWEEP) | tbit(T_RESTRICT) | tbit(T_CYCLE) | tbit(T_GUESS);
 constexpr unsigned T_FPS = tbit(T_FPS_DCT) | tbit(T_FPS_TRI) | tbit(T_FPS_IDCT);
 
-// kind -> (elapsed ms, weighted count) of ns_stats, of ns_scalar_stats, of ns_derived_stats, of ns_tracer_stats or of
-// ns_avg_stats.  A new timed line: one enum value, one row
+// kind -> (elapsed ms, weighted count) of ns_stats, of ns_scalar_stats, of ns_derived_stats, of ns_tracer_stats, of
+// ns_avg_stats or of ns_load_stats.  A new timed line: one enum value, one row
 struct TLine {
     double ns_stats::*t;
     int32_t ns_stats::*n;
@@ -38,6 +38,8 @@ struct TLine {
     int32_t ns_tracer_stats::*pn = nullptr;
     double ns_avg_stats::*at = nullptr;
     int32_t ns_avg_stats::*an = nullptr;
+    double ns_load_stats::*lt = nullptr;
+    int32_t ns_load_stats::*ln = nullptr;
 };
 inline const TLine& tline(TKind k) {
     static const TLine tab[T_NKIND] = {
@@ -57,6 +59,7 @@ inline const TLine& tline(TKind k) {
         {nullptr, nullptr, nullptr, nullptr, &ns_derived_stats::t_kernel_ms, &ns_derived_stats::n_kernels},   // T_DERIVED
         {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &ns_tracer_stats::t_kernel_ms, &ns_tracer_stats::n_kernels},   // T_TRACER
         {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &ns_avg_stats::t_kernel_ms, &ns_avg_stats::n_kernels},   // T_AVG
+        {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &ns_load_stats::t_kernel_ms, &ns_load_stats::n_kernels},   // T_LOADS
         {nullptr, nullptr, nullptr, nullptr},                                                // T_RAW
     };
     return tab[k];
@@ -150,14 +153,14 @@ public:
     // add the closed intervals of `kinds` (a mask of tbit) to the stats (any may be null: those figures are
     // dropped) and release them.  The caller knows the stream has passed them
     int drain(unsigned kinds, ns_stats* st, ns_scalar_stats* sc = nullptr, ns_derived_stats* dv = nullptr,
-              ns_tracer_stats* tr = nullptr, ns_avg_stats* av = nullptr) {
+              ns_tracer_stats* tr = nullptr, ns_avg_stats* av = nullptr, ns_load_stats* lo = nullptr) {
         int err = 0;
         for (size_t i = 0; i < iv_.size(); i++) {
             Iv& v = iv_[i];
             if (v.state != CLOSED || !(kinds >> v.kind & 1)) continue;
             const TLine& L = tline(v.kind);
             float ms = 0.f;
-            if ((st && L.t) || (sc && L.st) || (dv && L.dt) || (tr && L.pt) || (av && L.at)) {
+            if ((st && L.t) || (sc && L.st) || (dv && L.dt) || (tr && L.pt) || (av && L.at) || (lo && L.lt)) {
                 const int e = Api::elapsed(&ms, v.a, v.b);
                 if (e && !err) err = e;
                 if (!e && st && L.t) { st->*L.t += ms; if (L.n) st->*L.n += v.weight; }
@@ -165,6 +168,7 @@ public:
                 if (!e && dv && L.dt) { dv->*L.dt += ms; dv->*L.dn += v.weight; }
                 if (!e && tr && L.pt) { tr->*L.pt += ms; tr->*L.pn += v.weight; }
                 if (!e && av && L.at) { av->*L.at += ms; av->*L.an += v.weight; }
+                if (!e && lo && L.lt) { lo->*L.lt += ms; lo->*L.ln += v.weight; }
             }
             release((int)i);
         }

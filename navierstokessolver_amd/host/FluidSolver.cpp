@@ -26,6 +26,7 @@ struct Options {
     bool derived = false;   // -derived: Derived_<iter>.csv beside every export, one summary line after the last step
     std::string tracers;    // -tracers seeds.csv: particles carried by the step, Tracers_<iter>.csv beside every export
     int averages = 0;       // -averages N: running means and Reynolds stresses of u, v, P every N steps, Averages.csv after the last
+    int loads = 0;          // -loads N: the edges' wall loads every N steps, Loads.csv after the last
 };
 Options g_opt;
 
@@ -55,6 +56,8 @@ PetscErrorCode PetscInitialize(int* argc, char*** argv, const char*, const char*
             g_opt.tracers = next();
         } else if (!std::strcmp(a, "-averages")) {
             g_opt.averages = std::atoi(next());
+        } else if (!std::strcmp(a, "-loads")) {
+            g_opt.loads = std::atoi(next());
         } else {
             keep.push_back((*argv)[k]);  // positional arguments (grid file, sim file) stay
         }
@@ -328,6 +331,27 @@ void write_averages_csv(ns_solver* gpu, Grid& g) {
     std::fclose(f);
 }
 
+// -loads: the records the ring holds after the last step (ns_loads_history), one line per record and edge: the
+// record's step, the edge index and the eight sums
+void write_loads_csv(ns_solver* gpu, int n_edges, long long held) {
+    vector<int64_t> step((size_t)held);
+    vector<double> rec((size_t)held * n_edges * NS_LOAD_NUM);
+    if (ns_loads_history(gpu, 0, held, step.data(), rec.data()) != 0) {
+        cout << "Loads failed: " << ns_last_error() << "\n";
+        return;
+    }
+    FILE* f = std::fopen("Loads.csv", "w");
+    if (!f) return;
+    std::fprintf(f, "Step,Edge,Len,Fpx,Fpy,Fvx,Fvy,Q,Heat,HeatAdv\n");
+    for (long long r = 0; r < held; r++)
+        for (int e = 0; e < n_edges; e++) {
+            std::fprintf(f, "%lld,%d", (long long)step[(size_t)r], e);
+            for (int k = 0; k < NS_LOAD_NUM; k++) std::fprintf(f, ",%.17g", rec[((size_t)r * n_edges + e) * NS_LOAD_NUM + k]);
+            std::fprintf(f, "\n");
+        }
+    std::fclose(f);
+}
+
 }  // namespace
 
 void FluidSolver::Solve() {
@@ -355,6 +379,12 @@ void FluidSolver::Solve() {
         const ns_avg_desc ad{g_opt.averages, NS_AVG_SECOND | NS_AVG_PRESSURE};   // (no scalar in this driver: no T)
         if (ns_avg_enable(m.gpu, &ad) == 0) avg = true;
         else cout << "Averages failed: " << ns_last_error() << "\n";
+    }
+    bool loads = false;         // -loads: enabled likewise
+    if (g_opt.loads != 0) {
+        const ns_load_desc ld{g_opt.loads, 4096};
+        if (ns_loads_enable(m.gpu, &ld) == 0) loads = true;
+        else cout << "Loads failed: " << ns_last_error() << "\n";
     }
     int iter = 1;
     do {
@@ -401,6 +431,13 @@ void FluidSolver::Solve() {
             write_averages_csv(m.gpu, *grid);
             printf("averages: n=%lld steps=%lld\n", (long long)as.n, (long long)as.steps);
         } else cout << "Averages failed: " << ns_last_error() << "\n";
+    }
+    if (loads) {
+        ns_load_stats ls{};
+        if (ns_loads_last(m.gpu, &ls) == 0) {
+            write_loads_csv(m.gpu, (int)grid->edges.size(), (long long)ls.held);
+            printf("loads: records=%lld steps=%lld\n", (long long)ls.held, (long long)ls.steps);
+        } else cout << "Loads failed: " << ns_last_error() << "\n";
     }
     fflush(stdout);
     cout << "Solution Complete!\n";

@@ -313,6 +313,67 @@ class GpuSolver:
         self._avg_kept = (0.0, 0)
         return {"n": n, "steps": steps, "t_kernel_ms": t, "n_kernels": k}
 
+    # ---- wall loads (ns_loads_*: one rank)
+    _LOAD_KEYS = ("len", "fpx", "fpy", "fvx", "fvy", "q", "heat", "heat_adv")   # NS_LOAD_LEN .. NS_LOAD_HEAT_ADV
+    _FACE_KEYS = ("s", "ds", "p", "tx", "ty", "un", "tb", "qn")
+
+    def enable_loads(self, every: int = 1, capacity: int = 4096) -> None:
+        """The scheme's boundary fluxes summed per edge on the device: step k since here (or reset_loads) with
+        k % every == 0 appends one record of the state it starts from to a ring of `capacity` records.  Once per
+        solver."""
+        desc = L.NsLoadDesc(int(every), int(capacity))
+        L.check(L.lib().ns_loads_enable(self._h, ctypes.byref(desc)))
+
+    def loads(self) -> list:
+        """The current fields' sums, one dict per edge: len, fpx, fpy (pressure force on the wall), fvx, fvy (viscous),
+        q (flow rate out), heat (conductive heat rate out), heat_adv."""
+        n = len(self.grid.edges)
+        out = np.empty((n, L.NS_LOAD_NUM), dtype=np.float64)
+        L.check(L.lib().ns_loads_edges(self._h, _dptr(out)))
+        return [dict(zip(self._LOAD_KEYS, (float(x) for x in row))) for row in out]
+
+    def wall_faces(self, edge: int) -> dict:
+        """The boundary faces of one edge in ascending s: arrays s, ds, p, tx, ty, un, tb, qn of the current fields."""
+        n = ctypes.c_int64()
+        L.check(L.lib().ns_loads_face_count(self._h, int(edge), ctypes.byref(n)))
+        arrs = {k: np.empty(n.value, dtype=np.float64) for k in self._FACE_KEYS}
+        out = L.NsLoadFaces(*[_dptr(arrs[k]) for k in self._FACE_KEYS])
+        L.check(L.lib().ns_loads_faces(self._h, int(edge), ctypes.byref(out)))
+        return arrs
+
+    def load_history(self) -> tuple:
+        """(steps[held], records[held, n_edges, 8]) of the ring, oldest first; a record's step is the step number
+        since enable / reset, -1 for one taken by sample_loads."""
+        held = self._load_counts()[1]
+        steps = np.empty(held, dtype=np.int64)
+        rec = np.empty((held, len(self.grid.edges), L.NS_LOAD_NUM), dtype=np.float64)
+        L.check(L.lib().ns_loads_history(self._h, 0, held, steps.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                         _dptr(rec)))
+        return steps, rec
+
+    def sample_loads(self) -> None:
+        """One record of the current fields between steps, its step -1."""
+        L.check(L.lib().ns_loads_sample(self._h))
+
+    def reset_loads(self) -> None:
+        L.check(L.lib().ns_loads_reset(self._h))
+        self._load_kept = (0.0, 0)
+
+    def _load_counts(self):
+        # (the counters without losing ns_loads_last's kernel time, which is handed out once: kept for load_stats)
+        st = L.NsLoadStats()
+        L.check(L.lib().ns_loads_last(self._h, ctypes.byref(st)))
+        keep = getattr(self, "_load_kept", (0.0, 0))
+        self._load_kept = (keep[0] + st.t_kernel_ms, keep[1] + st.n_kernels)
+        return st.total, st.held, st.steps
+
+    def load_stats(self) -> dict:
+        """total, held, steps since enable / reset and the sampling kernels' time since the last call (timing on)."""
+        total, held, steps = self._load_counts()
+        t, k = self._load_kept
+        self._load_kept = (0.0, 0)
+        return {"total": total, "held": held, "steps": steps, "t_kernel_ms": t, "n_kernels": k}
+
     # ---- passive scalar (ns_scalar_*: one rank's rectangle)
     def enable_scalar(self, pe: float, bc) -> None:
         """A scalar T carried by the step, Peclet number pe.  bc: one ("dirichlet", value) or ("zerograd",)
