@@ -9,8 +9,8 @@
 // The reference's Krylov solves (GMRES+ILU, BCGSL+BJacobi, rtol 1e-8,
 // FluidSolver.cpp:61-82) are replaced by red-black SOR sweeps run to the same
 // relative-residual tolerance, checked every few sweeps from a fused residual.
-#include <rccl/rccl.h>
-#include <rocblas/rocblas.h>
+// The solver's state and what this file shares with the observers of the flow (ns_observe.cpp: derived fields,
+// tracers, flow statistics, wall loads) are in ns_solver.h.
 #include <rocsolver/rocsolver.h>
 #include <dlfcn.h>
 #include <limits>
@@ -21,20 +21,16 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
-#include <string>
 #include <type_traits>
-#include <vector>
 
-#include "../../include/nsgpu.h"
 #include "ns_fps_tables.h"
-#include "ns_internal.h"
-#include "ns_timing.h"
+#include "ns_solver.h"
 
-namespace {
+using namespace nss;
 
-thread_local std::string g_err;
+static thread_local std::string g_err;   // (ns_last_error's text)
 
-void set_err(const char* fmt, ...) {
+void nss::set_err(const char* fmt, ...) {
     char buf[1024];
     va_list ap;
     va_start(ap, fmt);
@@ -42,409 +38,6 @@ void set_err(const char* fmt, ...) {
     va_end(ap);
     g_err = buf;
 }
-
-#define HIPCHK(x)                                                                        \
-    do {                                                                                 \
-        hipError_t e_ = (x);                                                             \
-        if (e_ != hipSuccess) {                                                          \
-            set_err("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return NS_EHIP;                                                              \
-        }                                                                                \
-    } while (0)
-
-#define NCCLCHK(x)                                                                          \
-    do {                                                                                    \
-        ncclResult_t r_ = (x);                                                              \
-        if (r_ != ncclSuccess) {                                                            \
-            set_err("%s failed: %s (%s:%d)", #x, ncclGetErrorString(r_), __FILE__, __LINE__); \
-            return NS_ERCCL;                                                                \
-        }                                                                                   \
-    } while (0)
-
-#define CHK(x)                 \
-    do {                       \
-        int rc_ = (x);         \
-        if (rc_ != 0) return rc_; \
-    } while (0)
-
-// device scalar slots
-enum {
-    S_DIVSUM = 0,   // 2: sum rhs, sum rhs^2
-    S_SHIFT = 2,    // 2: mean, ||rhs - mean||^2
-    S_HBN = 4,      // 2: ||ru||^2, ||rv||^2
-    S_RES = 6,      // 2: residual^2 (u, v) or (phi, -)
-    S_MM = 8,       // 4: umin, -umax, vmin, -vmax
-    S_AUX = 12,     // 4
-    S_KSHIFT = 16,  // 1: the Krylov solves' shift after consistent_rhs (see there)
-    // multi-rank scalar bus (r5, bus()): this rank's partial values, gathered from every rank and folded
-    // into the global slots above -- K1's ||RHS||^2 (-> S_HBN), the Helmholtz residuals (-> S_RES, S_AUX)
-    // and the previous K5's min / max (-> S_MM); contiguous, in this order
-    S_HBNL = 18,    // 2
-    S_RESL = 20,    // 2
-    S_AUXL = 22,    // 2
-    S_MML = 24,     // 4
-    S_KRY = 28,     // 7: (r5) a BiCGStab batch's verdict for the host (KS_STOP, KS_BRK, KS_IT, KS_R2, r.r, alpha, omega)
-    S_OE = 35,      // 1: (r6) slabs with an E outflow: mode 0's projected shift 2 f'_{n-1}, all-reduced
-    S_NUM = 36
-};
-constexpr int BUS_NV = 10, BUS_NSUM = 6;
-
-// the step's kernel timings: the recorder of ns_timing.h over HIP events (nsg::HipTiming)
-using Timing = nsg::Timing<nsg::HipTiming>;
-#define TCHK(x) HIPCHK(static_cast<hipError_t>(x))
-
-}  // namespace
-
-// one multigrid level (level 0 = the solver's own PHI / TMP / RPHI arrays)
-struct MgLevel {
-    nsg::Geo g{};
-    nsg::Coef c{};
-    double *phi = nullptr, *tmp = nullptr, *b = nullptr;  // current iterate, ping-pong partner, rhs
-    double* mem = nullptr;                               // planes (levels >= 1)
-    double* coef = nullptr;                              // coefficient tables (levels >= 1)
-    std::vector<double> hx, hy;                          // host spacings
-    int minrows = 0;                                     // fewest rows any rank holds of this level
-    // coarse-level agglomeration (nranks > 1): a replicated level lives WHOLE on every rank
-    // (g.i0 = 0, g.nxl = g.nx) and is smoothed with no exchange.  The first replicated level
-    // is reached from the last distributed one through this rank's slab of it (gs) and
-    // gathered (every rank's rows si0[q] .. si0[q] + sn[q]) after the restriction.
-    bool repl = false;
-    // multi-rank: the rhs ghost rows are owed -- they travel with the level's next overlapped
-    // FUSE_R exchange instead of in an exchange round of their own (flush_b otherwise)
-    bool b_pend = false;
-    // the level's iterate is identically zero but not stored (the restriction from the level
-    // above skipped its phi := 0 writes): its first pass -- the fused restriction pass or the LDS
-    // coarse V-cycle -- takes it as zero without reading it or its ghost rows; any other consumer
-    // materialises the zeros first (zero_phi)
-    bool zero = false;
-    // multi-rank: the iterate's 5 ghost rows were sent right after this level's fused restriction
-    // pass (riding on the next exchange group down the V-cycle): the prolongation pass needs no
-    // exchange of its own for them -- phi is not written in between
-    bool phi_ghost = false;
-    nsg::Geo gs{};
-    std::vector<int> si0, sn;
-};
-
-struct ns_solver {
-    nsg::Knobs k;                // the NSGPU_* environment at ns_create (ns_knobs.h): fixed for the solver's life
-    nsg::Geo g{};
-    nsg::Coef c{};
-    int device = 0;
-    hipStream_t st = nullptr;
-    double dt = 0, re = 0, rtol = 1e-8, omega = 0, omega_v = 1.0;
-    int poisson = NS_POISSON_MG, max_iters = 200000, check_every = 0, timing = 0;
-    double* base = nullptr;      // all fields
-    size_t plane = 0;            // doubles per field plane
-    double* arr[NS_NUM_ARR] = {};  // pointer to local row 0 of each field
-    double* coef = nullptr;      // device coefficient tables
-    double* part = nullptr;      // per-block partials
-    double* scal = nullptr;      // device scalars
-    double* hs = nullptr;        // pinned host mirror of scal
-    int rank = 0, nranks = 1;
-    ncclComm_t comm = nullptr;
-    double ncells = 0;           // global cell count
-    // timed steps (timing == 1): every timed kernel call is an interval of this recorder, by kind (ns_timing.h) --
-    // drained where a host sync has passed them: the multigrid's at each residual check, the Helmholtz passes', K1's
-    // and the wall bands' after helm_solve, K5's at the next host sync (the next step's, after ns_step_async), the
-    // direct solve's after waiting for its own last event, the scalar's in scalar_end
-    Timing tm;
-    int helm_batch0 = 4, pois_batch0 = 8;
-    int helm_next = 4;           // first Helmholtz batch of the next step (adaptive unless check_every)
-    int helm_adapt = 1;
-    // the Helmholtz wall bands (k.helm_band): their width (cells from a wall: min(nx, ny) / 32) and RB-SOR sweeps (a
-    // multiple of 3).  (r6) k.band6, 6 band sweeps as ONE k_helm_band6 launch + copy-back: half the band bytes, but
-    // the launches are latency-bound, not HBM-bound -- 100 + 13 us against 2 x 48.5 (profiles/r06/ab/): off
-    int band_w = 128, band_sweeps = 6;
-    int helm_probe = 0;          // steps since the Helmholtz first-pass residual was last sampled
-    int phi_extrap = 3;          // Poisson initial guess: 0 phi^{n-1}, 1 linear, 2 quadratic, 3 (default) cubic while
-                                 // the last solve took > 1 V-cycle, else quadratic; 0 on a direct solve (choose_paths)
-    double mg_rate2 = 0.0;       // last measured per-cycle contraction of ||r||^2
-    int mg_hist[4] = {-1, -1, -1, -1};   // V-cycles the last four solves converged at (first check)
-    double* phim = nullptr;      // phi^{n-2} (the extrapolation's second point; rotates with PHI / TMP)
-    double* phim2 = nullptr;     // phi^{n-3} (quadratic / cubic extrapolation)
-    double* phim3 = nullptr;     // phi^{n-4} (cubic extrapolation)
-    double* phim4 = nullptr;     // phi^{n-5} (quartic, NSGPU_PHI_EXTRAP=4: A/B only)
-    double* phim_mem = nullptr;  // the extra planes' allocation
-    float* f32_mem = nullptr;    // fp32-field sweep planes (configs[4]), allocated on first use
-    float* f32[3] = {};          // phi, its ping-pong partner, rhs_phi (rows of g.ld floats)
-    int phim_valid = 0;          // history planes holding data (0 after a reset / an injected phi)
-    // multi-rank: ghost-row exchanges of the two-sweep passes run on a comm stream while the
-    // pass's interior strips run (NSGPU_OVERLAP=0: exchange, then the whole pass)
-    int overlap = 1;
-    int helm_b_pend = 0;          // RHS_u / RHS_v ghost rows owed to the first Helmholtz pair pass
-    // ghost-row requests riding on the NEXT exchange group (halo_reqs / gather_level), e.g. a
-    // multigrid level's post-restriction iterate (MgLevel::phi_ghost)
-    struct Piggy { const nsg::Geo* g; double* f; int w; };
-    Piggy piggy[4];
-    int npiggy = 0;
-    hipStream_t cst = nullptr;
-    // multi-rank: CUs reserved for the comm stream (its RCCL kernels run beside the compute
-    // stream's strips instead of queueing behind them; NSGPU_COMM_CUS, 0 = no masks)
-    int comm_cus = 0, compute_cus = 0;
-    hipEvent_t xev[2] = {nullptr, nullptr};
-    hipEvent_t fev = nullptr;     // fetch_begin / fetch_end: the scalars' copy to the host is done
-    int k1_red_nb = 0;            // (r7) K1''s partials wait for the Helmholtz check's reduction launch (their count)
-    // ns_step_async: the step's min/max travel to mm_host behind the step's last kernel (mev);
-    // read by the next ns_step_async (after that step's first host sync) or by ns_monitor
-    double* mm_host = nullptr;
-    hipEvent_t mev = nullptr;
-    int mm_pending = 0;
-    int extrap_pending = 0;       // ns_step: the phi extrapolation waits to hide a host sync
-    std::vector<MgLevel> lv;     // multigrid hierarchy (NS_POISSON_MG)
-    int mg_pre = 2, mg_post = 2, mg_coarse_iters = 0;
-    double mg_omega_c = 1.0, mg_omega_s = 1.1;
-    bool mg_coarse_lds = false;
-    // r4: the coarsest level solved exactly by its separable eigen-decomposition (k_direct, two
-    // launches): the first whole coarse level of <= k.direct_cells cells (default 128^2; 0 = the LDS
-    // V-cycle below it as in round 3).  dmat: P1 = Vx^-1, Q1 = Vy^-T, E, P2 = Vx,
-    // Q2 = Vy^T (direct_setup), padded to multiples of 16
-    // r4: a V-cycle boundary on the finest level in one pass (k_sweep4, k.fuse4): cycle c's prolongation
-    // pass is deferred when c's output is not checked (p_pending) and runs fused with cycle c+1's
-    // restriction pass
-    bool p_pending = false;
-    // r4: the phi extrapolation formed inside the solve's first restriction pass (k_sweep2_gin) instead
-    // of by k_axpby: extrapolate_phi only rotates the planes and leaves the guess's sources here;
-    // K3 then runs speculatively behind the Helmholtz check.  Measured (r4, 4096^2 driver form): the
-    // pass takes 241 us (184 VGPRs, 2 waves / SIMD, five streams) against FUSE_R 87 + k_axpby 104 us,
-    // 9,924-9,961 vs 9,957-10,143 MLUPS -- so opt-in (k.gin); default k_axpby (round 3)
-    bool gin_pending = false;
-    const double* gin_src[4] = {nullptr, nullptr, nullptr, nullptr};
-    double gin_c[4] = {0, 0, 0, 0};
-    bool mg_direct = false;
-    double* dmat = nullptr;
-    const double *dP1 = nullptr, *dQ1 = nullptr, *dE = nullptr, *dP2 = nullptr, *dQ2 = nullptr;
-    // NEUMANN outflow (pois_solve_krylov): BiCGStab planes r, r0, p, v, s, t, ph, sh, scratch
-    // (null without an outflow side) and the recurrence scalars
-    double* kv[9] = {};
-    double* kv_mem = nullptr;
-    double* lrow = nullptr;      // outflow preconditioner: its line solution (one row, in kv_mem)
-    double* cvimg = nullptr;     // the LDS coarse V-cycle's image (nsg::cv_image), cv_n doubles
-    int cv_n = 0, cv_dn = 0;
-    double* ksc = nullptr;
-    bool pc_active = false;      // inside mg_precond: level 0 has no mean shift
-    bool krylov_mg = false;      // the Poisson BiCGStab is preconditioned by a V-cycle (else Jacobi)
-    // the outflow preconditioner: a rectangle whose only NEUMANN side is W (0) or
-    // E (1): the V-cycle's hierarchy closes that side with a Dirichlet-centre ghost whose data,
-    // on the finest level, is the side's 1-D line solve (launch_line_solve); -1 = walls
-    int out_side = -1;
-    bool consist = false;        // stretched grid, no outflow: consistent_rhs() before every Poisson solve
-    bool fps_xuni = true;        // (r6) the direct solve's hx is uniform (false: x-stretched, unfused, no pivot fixed points)
-    // (r6) the dense y transforms (hy stretched, or an ny no FFT plan takes): Ly's eigenvectors through rocSOLVER's
-    // tridiagonal eigensolver at create, the transforms as rocBLAS GEMMs (F: forward, G: inverse, N x N each)
-    bool fps_dense = false;
-    rocblas_handle rb = nullptr;
-    double area = 0.0;           // sum of the domain's cell areas
-    double inv_area = 0.0;       // sum of their reciprocals
-    int32_t* fc_mem = nullptr;   // masked domain: topology plane (g.fc) and edge table (g.et)
-    int32_t* mband_tiles = nullptr;   // (r6) masked, one rank: the (li0, j0) of the mt tiles holding a wall-band cell
-    int mband_n = 0;
-    int32_t* ecell_mem = nullptr;   // (r5) masked domain: the slab's domain cells that are not FC_DEEP (g.ecell)
-    nsg::EdgeDev* et_mem = nullptr;
-    std::vector<nsg::EdgeDev> et_host;   // ... and its host copy (re-uploaded when an edge's profile pointer changes)
-    // edge profiles (ns_edge_profile): per edge its type and normal, the rectangle side it covers (-1 on a masked
-    // domain) and the device table of 2 info(k) with its host copy (ny entries for an x-normal edge, nx for a y-normal
-    // one; allocated on first use)
-    struct EdgeProf {
-        int type = 0, enx = 0, eny = 0, side = -1;
-        std::vector<double> host;
-        double* tab = nullptr;
-    };
-    std::vector<EdgeProf> eprof;
-    ns_host_transport ht{};      // host transport (ht.exchange != NULL) instead of RCCL
-    double* stage = nullptr;     // pinned staging for the host transport
-    size_t stage_n = 0;
-    // masked domain: this slab's bounding-box cells -> compact cell id - cid0 (-1 outside), so
-    // ns_get_fields / ns_set_fields speak the reference's compact Vec order (Grid.cpp:149-162)
-    std::vector<int32_t> cid;
-    int64_t cid0 = 0, ncid = 0;  // first compact id of the slab and its in-domain cell count
-    std::vector<double> hbuf;    // host bounding-box staging for that gather / scatter
-    // NSGPU_RCCL_LOOPBACK=1 (test / measurement hook): a 1-rank RCCL communicator whose every
-    // peer is this process.  One rank: every exchange point of the step runs its RCCL group with
-    // peer == self (both ghost sides from this slab's own edge rows) and every reduction an
-    // ncclAllReduce -- the multi-rank call sites on one GPU; ghost rows beyond the walls carry
-    // zero weight, so the step is the plain single-rank step.  nranks > 1 with neither an
-    // ncclUniqueId nor a host transport: a VIRTUAL slab -- rank `rank`'s slab, hierarchy,
-    // launches and RCCL groups (exchanges, the agglomeration gather) with self as every peer,
-    // reductions over this slab only: the per-rank time of a multi-GPU step without the other
-    // GPUs (tools/slab_projection.py).
-    int loopback = 0;
-    // virtual slab only (NSGPU_VIRTUAL_ITERS="h:c,h:c,..."): the slab's own residuals are not the
-    // global solve's, so each step replays the global run's Helmholtz sweeps h and V-cycles c
-    // (cycled over the list), with one residual check (host sync) per solve like a predicted one
-    std::vector<std::pair<int, int>> replay;
-    size_t replay_k = 0;
-    int rp_h = 0, rp_c = -1;        // this step's replayed counts (0 / -1: converge normally)
-    int n_xchg = 0, n_allred = 0;   // exchange groups / all-reduces issued in the current step
-    double x_link = 0.0;            // bytes over this rank's busiest peer link in the current step
-    // speculative CorrectVelocities: inside a time step, the multigrid's residual check that
-    // the cycle history predicts to pass enqueues K5 (into the ping-pong partners, with its
-    // min/max) BEFORE the host waits for the residual, so the GPU works through the host round
-    // trip; k5_spec = 1 after a passing check (the step then only swaps), 0 otherwise (K5 runs
-    // again after the last cycle: u* is untouched, K5 writes TMPU / TMPV)
-    int in_step = 0, k5_spec = 0, n_spec = 0, n_spec_hit = 0;
-    // (k.speculate = 0: no speculative K5 / K3, the equivalence test's reference)
-    // r4: K5 may form the next step's Poisson guess (k_cell_s<6>, k.k5_guess; default: k_axpby
-    // at the next step as in round 3); guess_ready: TMP holds it (branch guess_branch of extrap_plan) -- any entry
-    // point that may write TMP or the phi planes clears it.  K3 then runs speculatively behind the
-    // Helmholtz residual check (k3_spec: rhs_phi is this step's), which the extrapolation used to fill
-    // Measured (r4, 4096^2 driver form): k_cell_s<6> 242 us against K5 128 + k_axpby 104 us -- no gain
-    // (9,819-9,822 vs 9,821-9,863 MLUPS), so it is opt-in
-    int guess_ready = 0, guess_branch = 0, k3_spec = 0;
-    int cur_cycles = -1;         // V-cycles of the Poisson solve in progress (at its K5)
-    int last_cycles = -1;        // V-cycles of the last multigrid solve (-1: none / Krylov)
-    // r4: the direct Poisson solve (ns_fps.hip) of a rectangle with zero-flux phi sides and uniform hy
-    // (ny a power of two): DCT along y, tridiagonal recurrences along x, inverse DCT -- no iteration,
-    // so no initial guess (no phi history planes).  Its output residual (a separate pass: 76 us at
-    // 4096^2) is checked on the first solve of a run and every k.fps_check-th after it (default 16;
-    // 1 = every solve; a standalone ns_kernel solve always); the check's host sync hides
-    // behind a speculative K5, and a residual above rtol continues with multigrid V-cycles from this
-    // phi.  The solve is a fixed arithmetic sequence: its residual does not drift between checks
-    // (1e-13 .. 1e-12 of ||b|| at 4096^2).  NSGPU_FPS=0: multigrid
-    bool fps = false;
-    bool fps_pc = false;         // masked domain: the bounding box's direct solve preconditions BiCGStab (NSGPU_FPS_PC=0: V-cycle)
-    // (r5) and, with at most NSGPU_CAP_MAX (4096) interface faces, the exact solve by the capacitance matrix
-    // (cap_setup / cap_solve; NSGPU_CAP=0: BiCGStab preconditioned by the box's solve, A/B)
-    nsg::CapArgs cap{};
-    void* cap_mem = nullptr;
-    nsg::FpsArgs fa{};
-    // what the direct solve reads on the device beside fa (fps_setup; mem: its arena's ONE block, fa's arrays included)
-    struct FpsDev {
-        double* mem = nullptr;
-        const double *tw = nullptr, *wk = nullptr, *tw8 = nullptr;   // (r5) tw8, ny = 16384: the 8192-point halves' twiddles
-        // multi-rank: this rank's aggregate of a recurrence (2 x ld), every rank's (nranks x 2 x ld, one
-        // allgather per direction and solve) and the carry-in folded from them (ld)
-        double *ragg = nullptr, *gath = nullptr;
-        size_t n = 0;              // (r5) the allgather's slot: 2 x ld aggregates + (sum b, sum b^2) + padding
-        // (r5) ONE allgather per solve (NSGPU_FPS_ONEGATHER=0: two, A/B): the slot also carries the rank's backward
-        // aggregate with a zero forward carry-in (2 more ld), which is affine in that carry-in (FpsRank::bq); og_b /
-        // og_x1: the host tables B_p (every rank, per mode) and X1_p
-        bool og = false;
-        const double *og_b = nullptr, *og_x1 = nullptr;
-        // the deferred mean's tables of mode 0 (below): every chunk's E / BXl, the groups', the ranks' of the constant 1
-        const double *m0e = nullptr, *m0b = nullptr, *m0g = nullptr, *m0a = nullptr;
-        double *dense_mem = nullptr, *dF = nullptr, *dG = nullptr;   // the dense transforms (fps_dense): F | G
-    } fpd;
-    int fps_passes = 2;          // full passes of the tridiagonal recurrences (NSGPU_FPS_PASSES=3: t1 / t2 / t3)
-    long fps_solves = 0;
-    bool fps_og_mean = false;
-    // r5, multi-rank rectangles on the direct solve: the fused K3's sums are not all-reduced -- they ride
-    // on the recurrences' forward allgather (at 2 ld of each rank's slot), and the mean comes off mode 0
-    // afterwards, as the linear response of its aggregates to the constant ny * mean (fpd.m0*).
-    // NSGPU_FPS_DEFER=0: the all-reduce before the solve (A/B).  mean_pend: this step's sums wait there
-    bool fps_defer = false, mean_pend = false;
-    double fps_res = -1.0;       // the last checked solve's relative residual
-    int kpred[3] = {1, 1, 1};    // (r5) the last BiCGStab solve's iterations: Poisson, Helmholtz u, v (bicgstab's batch)
-    // (r5) a masked domain's Helmholtz solve on one rank by red-black SOR (k.mask_rb; k.mask_mt: up to 4 sweeps per
-    // launch + the residual in the last; k.mask_band wall-band sweeps first): the sweeps the last step needed (the
-    // next step's first batch)
-    int mask_helm_next = 4, mask_helm_ok = 0;
-    // r5, multi-rank rectangles: the Helmholtz check's collective is an allgather of every rank's
-    // S_HBNL .. S_MML (bus()): K1's norms and the previous step's K5 min / max ride on it, so neither
-    // takes a collective of its own (NSGPU_BUS=0: the per-reduction all-reduces, A/B); bus_mem holds
-    // the P gathered slots of BUS_NV values
-    bool bus = false;
-    double* bus_mem = nullptr;
-    // r5, multi-rank rectangles on the direct solve: DEEP ghost rows.  K1 computes its rows and deep_e =
-    // 8 + 6 R rows of each neighbour's slab (R: the wall bands' 3-sweep launches), its exchange carrying u,
-    // v, phi that deep; the band launches then compute 6 rows fewer each and need no exchange, and the
-    // residual 3-sweep pass finds its 7-row cone valid and computes one neighbour row more, which K3 reads --
-    // one exchange group (K1's) where r4 had 1 + R + 1 + 1 (deep_geo; NSGPU_DEEP=0: the r4 exchanges, A/B).  hp: the finest planes' ghost rows per side
-    // (HALO, or deep_e + HALO + 2); cu_ext / u_ext: ghost rows of cu, cv / of u, v (the Helmholtz
-    // iterates) known valid now
-    int hp = nsg::HALO;
-    bool deep = false;
-    int deep_e = 0, cu_ext = 0, u_ext = 0;
-    int phi_ext = 0;             // (r5) phi's ghost row valid from the direct solve (deep slabs, k_fps_t2b's ghost rows)
-    bool fps_strict = false;     // a check failed or came within 1/100 of rtol: check every solve
-    bool hbn_pend = false;       // slabs: K1's ||RHS||^2 partial sums await the Helmholtz check's all-reduce
-    // K3 fused into the direct solve's DCT (r4, launch_fps_div; NSGPU_FPS_FUSE=0: K3 + the DCT): inside
-    // steps the divergence goes straight into the transformed plane, rhs_phi is stored only for a checked
-    // solve; fps_pre: the plane holds this step's coefficients (pois_solve_fps skips its DCT)
-    bool fps_fuse = true, fps_pre = false, fps_pre_b = false;
-    // (r6) the deferred correction: an ns_step_async step ends after its Poisson solve (U, V = u*, v*, PHI = phi^n)
-    // and the next step's K1 applies CorrectVelocities on the fly (k_rhs_sc: K5 folded into K1 -- one HBM pass
-    // of 40 B/cell less); any other entry point that reads or writes the fields runs K5 first (materialize)
-    bool k5_defer_ok = false;    // one rank, rectangle, no NEUMANN side, the direct solve, hy uniform, streaming K1
-    int corr_pend = 0, defer_now = 0, corr_k1 = 0;   // corr_k1: this step's K1 applied a deferred correction
-    // a rectangle's edge on each side (W, E, S, N) and the grid's edge count: ns_scalar_enable's bc[k] is per edge
-    int side_edge[4] = {-1, -1, -1, -1}, n_edges = 0;
-    double inv_h2 = 0.0;         // 1 / min(hx)^2 + 1 / min(hy)^2 (the Helmholtz SOR weights)
-    // the passive scalar (ns_scalar_enable; DESIGN.md 4 "Passive scalar"): nothing below exists without one.
-    // Planes laid out like the fields: T, its sweep partner, rT, cT0; its ghosts per side (q_g = neu ? q : -q + c);
-    // ct: the coefficient tables with the scalar's Dirichlet sides in bx / by (the sweeps' operator I - dt/(2 pe)
-    // L_T); partials, device slots and their pinned mirror of its own, so that a step's other reductions see
-    // exactly what they see without a scalar
-    struct Scalar {
-        enum { BN2 = 0, RES2, TMIN, NTMAX, AUX, NSLOT = 8 };   // device slots
-        bool on = false;
-        double pe = 0.0, omega = 1.0;
-        int neu[4] = {0, 0, 0, 0};
-        double c[4] = {0, 0, 0, 0};
-        double *mem = nullptr, *T = nullptr, *TT = nullptr, *R = nullptr, *C = nullptr;
-        double* bxy = nullptr;
-        nsg::Coef ct{};
-        double *part = nullptr, *scal = nullptr, *hs = nullptr;
-        hipEvent_t ev = nullptr;
-        // the step's first batch of sweeps is what the previous step needed; it is enqueued, with its residual and
-        // the min / max of its result, before the velocities' Helmholtz solve, whose residual check brings them
-        int next = 4, ok_steps = 0, sweeps = 0;
-        ns_scalar_stats last{};
-        // Boussinesq buoyancy (ns_scalar_buoyancy): f = (bx, by) (T - tref), applied by k_rhs_t's buoyant variant
-        double bx = 0.0, by = 0.0, tref = 0.0;
-        bool buoyant() const { return on && (bx != 0.0 || by != 0.0); }
-    } sc;
-    // derived fields (ns_derive; DESIGN.md 4 "Derived fields"): nothing below exists before the first call.  The
-    // planes (nxl x ld, no ghost rows) and psi's vertex plane ((nx + 1) rows of ldv) each on first request; partials,
-    // result slots and their pinned mirror of its own, so that no slot a later step reads is touched
-    struct Derived {
-        enum { NSLOT = 16 };   // 3 sums, 4 + 2 minima, psi's (min, -max)
-        double *p = nullptr, *w = nullptr, *d = nullptr, *psi = nullptr, *base = nullptr;
-        double *part = nullptr, *ppart = nullptr, *scal = nullptr, *hs = nullptr;
-        int ncap = 0, ldv = 0;
-    } dv;
-    // tracer particles (ns_tracers_enable; DESIGN.md 4 "Tracers"): nothing below exists without them.  SoA planes of
-    // `cap` particles (x, y, wu, wv, age, then the int32 state words), the face tables xf | yf with their host copies
-    // (the seed check), partials, four count slots (live, exited, stuck, -max age) and their pinned mirror of its
-    // own; su / sv (ns_tracers_sample's output) on first use
-    struct Tracers {
-        enum { NSLOT = 4 };
-        bool on = false;
-        int64_t cap = 0, n = 0;
-        double *mem = nullptr, *smp = nullptr, *tab = nullptr;
-        double *part = nullptr, *scal = nullptr, *hs = nullptr;
-        std::vector<double> xf, yf;
-        nsg::TracerArgs a{};
-    } tr;
-    // running flow statistics (ns_avg_enable; DESIGN.md 4 "Flow statistics"): nothing below exists without them.
-    // mem: the means and co-moment sums accumulated (nxl x ld each, no ghost rows; plane[which], null: not kept) and,
-    // with NS_AVG_PRESSURE, the sample's own pressure plane P behind them; ppart: the derived pass's partials, of
-    // its own, so that no slot a step or ns_derive reads is touched.  n, steps: host counters
-    struct Averages {
-        bool on = false;
-        int every = 1, flags = 0, nsrc = 2;
-        int64_t n = 0, steps = 0;
-        size_t nplanes = 0;
-        double *mem = nullptr, *P = nullptr, *ppart = nullptr;
-        double* plane[NS_AVG_NUM] = {};
-        nsg::MomArgs a{};
-        ns_avg_stats acc{};      // the drained sample intervals nobody has asked for yet
-    } av;
-    // wall loads (ns_loads_enable; DESIGN.md 4 "Wall loads"): nothing below exists without them.  list: the host's
-    // boundary-face list (its s and ds tables are handed out from here); tab: its device copy (faces | chunks | chunk
-    // offsets); val: the faces' six values; part: the chunks' partials; ring: capacity + 1 records of nrec doubles, the
-    // last one ns_loads_edges' own.  The ring's counters and step numbers live on the host: slot = sample % capacity
-    struct Loads {
-        bool on = false;
-        int every = 1, capacity = 0, nrec = 0;
-        int64_t total = 0, steps = 0;
-        nsg::LoadList list;
-        int32_t* tab = nullptr;
-        double *val = nullptr, *part = nullptr, *ring = nullptr;
-        std::vector<int64_t> rstep;
-        nsg::LoadArgs a{};
-        ns_load_stats acc{};     // the drained sample intervals nobody has asked for yet
-    } lo;
-};
 
 namespace {
 
@@ -3068,7 +2661,7 @@ int div_mean(ns_solver* s, int nb) {
 int divergence_fps(ns_solver* s) {
     // (timed as the direct solve's forward transform; a speculative K3 formed again replaces its figure)
     Timing::Scope iv;
-    if (s->timing) (void)s->tm.drain(nsg::tbit(nsg::T_FPS_DCT), nullptr);
+    if (s->timing) (void)s->tm.drop(nsg::tbit(nsg::T_FPS_DCT));
     TCHK(s->tm.open(iv, nsg::T_FPS_DCT, s->timing));
     double* b = fps_checks_next(s) ? s->arr[NS_ARR_RPHI] : nullptr;
     auto launch = [&](int phase) {
@@ -3230,7 +2823,7 @@ int correct_launch(ns_solver* s, double* part2) {
     // K5 whose check failed runs again: its figure is replaced)
     const bool t5 = s->timing && s->in_step && !guess;
     Timing::Scope iv;
-    if (t5) (void)s->tm.drain(nsg::tbit(nsg::T_K5), nullptr);
+    if (t5) (void)s->tm.drop(nsg::tbit(nsg::T_K5));
     TCHK(s->tm.open(iv, nsg::T_K5, t5));
     auto launch = [&]() {
         if (guess)
@@ -3271,12 +2864,37 @@ int correct(ns_solver* s) {
 
 // (r6) a deferred correction applied now (K5 as in a synchronous step): before any entry point that reads or writes
 // the fields, the monitor, or runs kernels on them
-int materialize(ns_solver* s) {
+}  // namespace
+int nss::materialize(ns_solver* s) {
     if (!s->corr_pend) return 0;
     s->corr_pend = 0;
     HIPCHK(hipSetDevice(s->device));
     return correct(s);
 }
+
+// the observers' and the scalar's entry prologue (ns_solver.h)
+int nss::prepare(ns_solver* s, int flags) {
+    if (flags & SETTLE) CHK(materialize(s));
+    if (flags & LAUNCH) {
+        HIPCHK(hipSetDevice(s->device));
+        nsg::set_compute_cus(s->compute_cus);
+    }
+    return 0;
+}
+int nss::enter(ns_solver* s, const char* who, bool on, const char* what, const char* call, int flags) {
+    if (!s) { set_err("null solver"); return NS_EINVAL; }
+    if (!on) { set_err("%s: %s (%s)", who, what, call); return NS_EINVAL; }
+    return prepare(s, flags);
+}
+
+int nss::host_spacings(ns_solver* s, std::vector<double>& hx, std::vector<double>& hy) {
+    hx.resize(s->g.nx);
+    hy.resize(s->g.ny);
+    HIPCHK(hipMemcpy(hx.data(), s->c.hx, hx.size() * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(hy.data(), s->c.hy, hy.size() * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+namespace {
 
 // ---------------- the passive scalar (ns_scalar_enable): rT, then (I - dt/(2 pe) L_T) T^{n+1} = rT
 // the right-hand side from u^n, v^n, T^n, cT0 (k_rhs_t): cT0 <- cT in place, rT, ||rT||^2 -> its BN2 slot
@@ -3286,14 +2904,14 @@ int scalar_rhs(ns_solver* s) {
     TCHK(s->tm.open(iv, nsg::T_SCALAR_RHS, s->timing && s->in_step));
     // buoyancy: the variant that also folds the force into K1's RU / RV and CU / CV (which then hold convective-minus-
     // force) and sums the rewritten planes' squares into the partial block's third quarter
-    double* pf = q.part + 4 * (size_t)nsg::max_partials(s->g);
+    double* pf = q.part.get() + 4 * (size_t)nsg::max_partials(s->g);
     const nsg::Buoy by{q.bx, q.by, q.tref, s->arr[NS_ARR_RU], s->arr[NS_ARR_RV], s->arr[NS_ARR_CU], s->arr[NS_ARR_CV], pf};
     const bool fb = q.buoyant();
     const int nb = nsg::launch_rhs_t(s->k, s->g, s->c, q.neu, q.c, s->dt, q.pe, s->arr[NS_ARR_U], s->arr[NS_ARR_V], q.T,
-                                     q.C, q.R, q.part, s->st, fb ? &by : nullptr);
+                                     q.C, q.R, q.part.get(), s->st, fb ? &by : nullptr);
     if (nb < 0) { set_err("the scalar's right-hand side: launch refused"); return NS_EHIP; }
     TCHK(iv.close());
-    nsg::launch_reduce_sum(q.part, nb, 1, q.scal + ns_solver::Scalar::BN2, s->st);
+    nsg::launch_reduce_sum(q.part.get(), nb, 1, q.scal.get() + ns_solver::Scalar::BN2, s->st);
     // the Helmholtz tolerance is relative to ||RHS||^2 (S_HBN): K1's norms of the forced components are stale -- for
     // a fluid at rest 0, which no residual is below -- so the rewritten planes' own norms replace them here, on the
     // stream behind K1's reduction (rhs() does not defer it while buoyancy is on) and before the Helmholtz check's read
@@ -3313,15 +2931,15 @@ int scalar_batch(ns_solver* s, int n) {
     int nb = 0;
     for (int k = 0; k < n; k += 2) {
         nb = nsg::launch_helm_sweep2(s->k, s->g, q.ct, alpha, q.omega, q.T, nullptr, q.TT, nullptr, q.R, nullptr,
-                                     k + 2 >= n ? q.part : nullptr, s->st, 1);
+                                     k + 2 >= n ? q.part.get() : nullptr, s->st, 1);
         if (nb < 0) { set_err("the scalar's Helmholtz pass: launch refused"); return NS_EHIP; }
         std::swap(q.T, q.TT);
     }
     q.sweeps += n;
-    double* pm = q.part + 2 * (size_t)nsg::max_partials(s->g);
+    double* pm = q.part.get() + 2 * (size_t)nsg::max_partials(s->g);
     const int nm = nsg::launch_minmax(s->g, q.T, pm, s->st);
-    nsg::launch_reduce_sum_min(q.part, nb, 1, q.scal + S::RES2, pm, nm, 2, q.scal + S::TMIN, s->st);
-    HIPCHK(hipMemcpyAsync(q.hs, q.scal, S::NSLOT * sizeof(double), hipMemcpyDeviceToHost, s->st));
+    nsg::launch_reduce_sum_min(q.part.get(), nb, 1, q.scal.get() + S::RES2, pm, nm, 2, q.scal.get() + S::TMIN, s->st);
+    HIPCHK(hipMemcpyAsync(q.hs.get(), q.scal.get(), S::NSLOT * sizeof(double), hipMemcpyDeviceToHost, s->st));
     HIPCHK(hipEventRecord(q.ev, s->st));
     return 0;
 }
@@ -3362,104 +2980,7 @@ int scalar_end(ns_solver* s) {
     CHK(scalar_wait(s));
     q.last.t_rhs_kernel_ms = 0.0;
     q.last.n_rhs_kernels = 0;
-    TCHK(s->tm.drain(nsg::tbit(nsg::T_SCALAR_RHS), nullptr, &q.last));
-    return 0;
-}
-
-// ---------------- tracer particles (ns_tracers_enable; DESIGN.md 4 "Tracers")
-// one advance of the particles by dt in the planes U, V hold now (inside a step: u^n, v^n, which K1 leaves there in the
-// deferred-K5 path too), on the solver's stream; count: the fates' counts and the largest live age reduced into the
-// tracers' own slots behind it (no slot of the step's is touched, no host sync)
-int tracer_advance(ns_solver* s, double dt, bool count) {
-    auto& q = s->tr;
-    q.a.g = s->g;   // (an edge profile set since the last launch changes the geometry's table pointers)
-    q.a.u = s->arr[NS_ARR_U];
-    q.a.v = s->arr[NS_ARR_V];
-    q.a.n = q.n;
-    q.a.dt = dt;
-    Timing::Scope iv;
-    TCHK(s->tm.open(iv, nsg::T_TRACER, s->timing));
-    const int nb = nsg::launch_tracer(q.a, count ? 2 : 1, s->st);
-    if (nb < 0) { set_err("the tracer kernel's launch was refused"); return NS_EHIP; }
-    TCHK(iv.close());
-    if (count) nsg::launch_reduce_sum_min(q.part, nb, 3, q.scal, q.part + 3 * (size_t)nb, nb, 1, q.scal + 3, s->st);
-    return 0;
-}
-
-// ---------------- running flow statistics (ns_avg_enable; DESIGN.md 4 "Flow statistics")
-// one sample of the planes U, V (PHI, T) hold now into the running means and co-moment sums, on the solver's stream
-// (inside a step: u^n, v^n, phi^n, T^n right behind K1, which leaves them there in the deferred-K5 path too).  The
-// pressure first, by the derived fields' cell pass storing P only, into the statistics' own plane.  n and w are
-// host-side: no sync, no readback
-int avg_sample(ns_solver* s) {
-    auto& q = s->av;
-    nsg::MomArgs& a = q.a;
-    const bool has_t = (q.flags & NS_AVG_SCALAR) != 0, has_p = (q.flags & NS_AVG_PRESSURE) != 0;
-    a.src[0] = s->arr[NS_ARR_U];
-    a.src[1] = s->arr[NS_ARR_V];
-    if (has_t) a.src[2] = s->sc.T;   // (the scalar's current plane: its sweeps swap T and its partner)
-    if (has_p) {
-        Timing::Scope iv;
-        TCHK(s->tm.open(iv, nsg::T_AVG, s->timing));
-        const int nb = nsg::launch_derived(s->k, s->g, s->c, s->dt / (2 * s->re), s->arr[NS_ARR_U], s->arr[NS_ARR_V],
-                                           s->arr[NS_ARR_PHI], q.P, nullptr, nullptr, q.ppart, s->st);
-        if (nb < 0) { set_err("flow statistics: the pressure pass's launch was refused"); return NS_EHIP; }
-        TCHK(iv.close());
-        a.src[q.nsrc - 1] = q.P;
-    }
-    a.w = 1.0 / (double)(q.n + 1);
-    Timing::Scope iv;
-    TCHK(s->tm.open(iv, nsg::T_AVG, s->timing));
-    if (nsg::launch_moments(a, q.nsrc, (q.flags & NS_AVG_SECOND) != 0, has_t, s->st) < 0) {
-        set_err("flow statistics: the moments kernel's launch was refused");
-        return NS_EHIP;
-    }
-    TCHK(iv.close());
-    q.n++;
-    return 0;
-}
-
-// ---------------- wall loads (ns_loads_enable; DESIGN.md 4 "Wall loads")
-// the boundary faces' values and the edges' sums of the planes U, V, PHI (T) hold now, on the solver's stream: the face
-// kernel, then (out != null) the edge sums into the record at out.  The geometry and the scalar's state are read per
-// launch: an edge profile or a scalar enabled since the last one changes them.  No sync, no readback
-int loads_run(ns_solver* s, double* out, bool timed) {
-    auto& q = s->lo;
-    nsg::LoadArgs& a = q.a;
-    a.g = s->g;
-    a.c = s->c;
-    a.alpha = s->dt / (2 * s->re);
-    a.re = s->re;
-    a.u = s->arr[NS_ARR_U];
-    a.v = s->arr[NS_ARR_V];
-    a.phi = s->arr[NS_ARR_PHI];
-    a.T = s->sc.on ? s->sc.T : nullptr;   // (the scalar's current plane: its sweeps swap T and its partner)
-    a.pe = s->sc.on ? s->sc.pe : 1.0;
-    for (int k = 0; k < 4; k++) {
-        a.tneu[k] = s->sc.neu[k];
-        a.tc[k] = s->sc.c[k];
-    }
-    {
-        Timing::Scope iv;
-        TCHK(s->tm.open(iv, nsg::T_LOADS, timed && s->timing));
-        if (nsg::launch_load_faces(a, s->st) < 0) { set_err("wall loads: the face kernel's launch was refused"); return NS_EHIP; }
-        TCHK(iv.close());
-    }
-    if (out) {
-        Timing::Scope iv;
-        TCHK(s->tm.open(iv, nsg::T_LOADS, timed && s->timing));
-        if (nsg::launch_load_edges(a, out, s->st) < 0) { set_err("wall loads: the edge sums' launch was refused"); return NS_EHIP; }
-        TCHK(iv.close());
-    }
-    return 0;
-}
-// one record appended to the ring: `step` and the sums of the current planes
-int loads_sample(ns_solver* s, int64_t step) {
-    auto& q = s->lo;
-    const int64_t slot = q.total % q.capacity;
-    CHK(loads_run(s, q.ring + (size_t)slot * q.nrec, true));
-    q.rstep[slot] = step;
-    q.total++;
+    TCHK(s->tm.drain(nsg::tbit(nsg::T_SCALAR_RHS), &q.last));
     return 0;
 }
 
@@ -3950,21 +3471,7 @@ int choose_paths(ns_solver* s, const ns_grid_desc* gd, const ns_params* p) {
     return 0;
 }
 
-// phase 4's allocations: `bytes` at *ptr, zeroed on s->st if `zero`; the error text and code otherwise
-template <class T>
-int dev_alloc(ns_solver* s, T** ptr, size_t bytes, bool zero, const char* what) {
-    if (hipMalloc(ptr, bytes) != hipSuccess) { set_err("hipMalloc of %zu bytes (%s) failed", bytes, what); return NS_ENOMEM; }
-    if (zero && hipMemsetAsync(*ptr, 0, bytes, s->st) != hipSuccess) { set_err("memset (%s) failed", what); return NS_EHIP; }
-    return 0;
-}
-// ... filled from the host vector v
-template <class T>
-int dev_upload(ns_solver* s, T** ptr, const std::vector<T>& v, const char* what) {
-    CHK(dev_alloc(s, ptr, v.size() * sizeof(T), false, what));
-    if (hipMemcpy(*ptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) { set_err("%s upload failed", what); return NS_EHIP; }
-    return 0;
-}
-
+// (phase 4's allocations: dev_alloc / dev_upload of ns_solver.h)
 // the device, the compute stream and (multi-rank / loopback) the comm stream with its events
 int create_streams(ns_solver* s) {
     const int dev = s->device;
@@ -4265,15 +3772,9 @@ int ns_parabolic_profile(const double* h, int32_t n, int32_t k0, int32_t k1, dou
 }
 
 static void scalar_free(ns_solver* s) {
-    auto& q = s->sc;
-    if (q.mem) (void)hipFree(q.mem);
-    if (q.bxy) (void)hipFree(q.bxy);
-    if (q.part) (void)hipFree(q.part);
-    if (q.scal) (void)hipFree(q.scal);
-    if (q.hs) (void)hipHostFree(q.hs);
-    if (q.ev) (void)hipEventDestroy(q.ev);
-    (void)s->tm.drain(nsg::tbit(nsg::T_SCALAR_RHS), nullptr);   // (its events stay with the recorder)
-    q = ns_solver::Scalar{};
+    if (s->sc.ev) (void)hipEventDestroy(s->sc.ev);
+    (void)s->tm.drop(nsg::tbit(nsg::T_SCALAR_RHS));   // (its events stay with the recorder)
+    s->sc = ns_solver::Scalar{};
 }
 
 void ns_destroy(ns_solver* s) {
@@ -4281,17 +3782,7 @@ void ns_destroy(ns_solver* s) {
     (void)hipSetDevice(s->device);
     if (s->st) (void)hipStreamSynchronize(s->st);
     scalar_free(s);
-    for (double* q : {s->dv.p, s->dv.w, s->dv.d, s->dv.psi, s->dv.base, s->dv.part, s->dv.ppart, s->dv.scal})
-        if (q) (void)hipFree(q);
-    if (s->dv.hs) (void)hipHostFree(s->dv.hs);
-    for (double* q : {s->tr.mem, s->tr.smp, s->tr.tab, s->tr.part, s->tr.scal})
-        if (q) (void)hipFree(q);
-    if (s->tr.hs) (void)hipHostFree(s->tr.hs);
-    for (double* q : {s->av.mem, s->av.ppart})
-        if (q) (void)hipFree(q);
-    for (double* q : {s->lo.val, s->lo.part, s->lo.ring})
-        if (q) (void)hipFree(q);
-    if (s->lo.tab) (void)hipFree(s->lo.tab);
+    observers_free(s);
     if (s->comm) (void)ncclCommDestroy(s->comm);
     if (s->mev) (void)hipEventDestroy(s->mev);
     if (s->mm_host) (void)hipHostFree(s->mm_host);
@@ -4357,7 +3848,7 @@ static int step_body(ns_solver* s, ns_stats& st) {
 static int step_body_(ns_solver* s, ns_stats& st) {
     // (intervals a standalone kernel call or a failed step left behind are dropped; K5's wait for their drain below)
     // (the flow statistics' intervals are kept: they add up until ns_avg_last asks)
-    (void)s->tm.drain(~(nsg::tbit(nsg::T_K5) | nsg::tbit(nsg::T_AVG) | nsg::tbit(nsg::T_LOADS)), nullptr);
+    (void)s->tm.drop(~(nsg::tbit(nsg::T_K5) | nsg::tbit(nsg::T_AVG) | nsg::tbit(nsg::T_LOADS)));
     CHK(rhs(s, true));                                             // ConstructRHS_V       (:546)
     // the flow statistics sample the state the step starts from -- u^n, v^n, phi^n, T^n -- directly behind K1 (after
     // it U, V hold u^n, v^n in the deferred-K5 path too), ahead of the scalar's first batch, which swaps T^n away,
@@ -4393,8 +3884,8 @@ static int step_body_(ns_solver* s, ns_stats& st) {
     // (helm_solve's last residual check synchronised the stream: behind the Helmholtz passes -- per component, 24
     // B/cell --, K1, the wall bands and the previous step's K5)
     TCHK(s->tm.drain(nsg::tbit(nsg::T_HELM) | nsg::tbit(nsg::T_K1) | nsg::tbit(nsg::T_BAND) | nsg::tbit(nsg::T_K5), &st));
-    if (s->av.on) TCHK(s->tm.drain(nsg::tbit(nsg::T_AVG), nullptr, nullptr, nullptr, nullptr, &s->av.acc));
-    if (s->lo.on) TCHK(s->tm.drain(nsg::tbit(nsg::T_LOADS), nullptr, nullptr, nullptr, nullptr, nullptr, &s->lo.acc));
+    if (s->av.on) TCHK(s->tm.drain(nsg::tbit(nsg::T_AVG), &s->av.acc));
+    if (s->lo.on) TCHK(s->tm.drain(nsg::tbit(nsg::T_LOADS), &s->lo.acc));
     if (!s->k3_spec) CHK(divergence(s));                           // ConstructRHS_phi + mean (:549-550)
     s->k3_spec = 0;
     CHK(consistent_rhs(s));                                        // stretched grids only
@@ -4569,570 +4060,6 @@ int ns_set_array(ns_solver* s, int which, const double* host) {
         for (int& h : s->mg_hist) h = -1;   // an injected state: no cycle-count history
     if (which == NS_ARR_RU || which == NS_ARR_RV) CHK(helm_bnorm(s));
     HIPCHK(hipStreamSynchronize(s->st));
-    return 0;
-}
-
-// ---------------- derived fields ("Derived fields"): P, vorticity, divergence, psi and the integrals of
-// the current u, v, phi.  One cell pass (24 B/cell in, only the planes asked for out) + psi's two launches + one
-// reduction, all on the solver's stream with buffers of its own
-int ns_derive(ns_solver* s, const ns_derived* out, ns_derived_stats* st) {
-    if (!s) { set_err("null solver"); return NS_EINVAL; }
-    if (!out && !st) { set_err("ns_derive: out and st are both NULL"); return NS_EINVAL; }
-    if (s->nranks > 1) { set_err("ns_derive: nranks > 1 is not supported"); return NS_EINVAL; }
-    CHK(materialize(s));
-    HIPCHK(hipSetDevice(s->device));
-    nsg::set_compute_cus(s->compute_cus);
-    using D = ns_solver::Derived;
-    auto& q = s->dv;
-    const nsg::Geo& g = s->g;
-    const ns_derived none{nullptr, nullptr, nullptr, nullptr};
-    const ns_derived& o = out ? *out : none;
-    const size_t pl = (size_t)g.nxl * g.ld * sizeof(double);
-    if (!q.part) {
-        q.ncap = nsg::derived_partials(g);
-        CHK(dev_alloc(s, &q.part, (size_t)q.ncap * 9 * sizeof(double), false, "derived partials"));
-        CHK(dev_alloc(s, &q.scal, D::NSLOT * sizeof(double), true, "derived slots"));
-        if (hipHostMalloc(&q.hs, D::NSLOT * sizeof(double), hipHostMallocDefault) != hipSuccess) { set_err("hipHostMalloc failed"); return NS_ENOMEM; }
-    }
-    if (o.p && !q.p) CHK(dev_alloc(s, &q.p, pl, true, "pressure plane"));
-    if (o.vort && !q.w) CHK(dev_alloc(s, &q.w, pl, true, "vorticity plane"));
-    if (o.div && !q.d) CHK(dev_alloc(s, &q.d, pl, true, "divergence plane"));
-    if (o.psi && !q.psi) {
-        q.ldv = (g.ny + 1 + 15) & ~15;
-        CHK(dev_alloc(s, &q.psi, (size_t)(g.nx + 1) * q.ldv * sizeof(double), true, "stream-function plane"));
-        CHK(dev_alloc(s, &q.base, (size_t)(g.nx + 1) * sizeof(double), false, "stream-function base"));
-        CHK(dev_alloc(s, &q.ppart, (size_t)(g.nx + 1) * 2 * sizeof(double), false, "stream-function partials"));
-    }
-    Timing::Scope iv;
-    TCHK(s->tm.open(iv, nsg::T_DERIVED, s->timing));
-    const int nb = nsg::launch_derived(s->k, g, s->c, s->dt / (2 * s->re), s->arr[NS_ARR_U], s->arr[NS_ARR_V],
-                                       s->arr[NS_ARR_PHI], o.p ? q.p : nullptr, o.vort ? q.w : nullptr,
-                                       o.div ? q.d : nullptr, q.part, s->st);
-    if (nb < 0) { set_err("ns_derive: the cell pass's launch was refused"); return NS_EHIP; }
-    TCHK(iv.close());
-    int np = 0;
-    if (o.psi) {
-        np = nsg::launch_psi(g, s->c, s->arr[NS_ARR_U], s->arr[NS_ARR_V], q.base, q.psi, q.ldv, q.ppart, s->st);
-        if (np < 0) { set_err("ns_derive: the stream function's launch was refused"); return NS_EHIP; }
-    }
-    nsg::launch_derived_reduce(q.part, nb, q.ncap, q.ppart, np, q.scal, s->st);
-    HIPCHK(hipMemcpyAsync(q.hs, q.scal, D::NSLOT * sizeof(double), hipMemcpyDeviceToHost, s->st));
-    const size_t wb = (size_t)g.ny * 8, ldb = (size_t)g.ld * 8;
-    if (o.p) HIPCHK(hipMemcpy2DAsync(o.p, wb, q.p, ldb, wb, g.nxl, hipMemcpyDeviceToHost, s->st));
-    if (o.vort) HIPCHK(hipMemcpy2DAsync(o.vort, wb, q.w, ldb, wb, g.nxl, hipMemcpyDeviceToHost, s->st));
-    if (o.div) HIPCHK(hipMemcpy2DAsync(o.div, wb, q.d, ldb, wb, g.nxl, hipMemcpyDeviceToHost, s->st));
-    if (o.psi)
-        HIPCHK(hipMemcpy2DAsync(o.psi, (size_t)(g.ny + 1) * 8, q.psi, (size_t)q.ldv * 8, (size_t)(g.ny + 1) * 8, g.nx + 1,
-                                hipMemcpyDeviceToHost, s->st));
-    HIPCHK(hipStreamSynchronize(s->st));
-    ns_derived_stats r{};
-    TCHK(s->tm.drain(nsg::tbit(nsg::T_DERIVED), nullptr, nullptr, &r));
-    const double* h = q.hs;
-    r.ke = 0.5 * h[0];
-    r.enstrophy = 0.5 * h[1];
-    r.div_l2 = std::sqrt(h[2]);
-    r.div_max = -h[3];
-    r.cfl = s->dt * -h[4];
-    r.vort_min = h[5];
-    r.vort_max = -h[6];
-    r.p_min = h[7];
-    r.p_max = -h[8];
-    r.psi_min = o.psi ? h[9] : NAN;
-    r.psi_max = o.psi ? -h[10] : NAN;
-    if (st) *st = r;
-    return 0;
-}
-
-// ---------------- tracer particles ("Tracers"): the entry points.  One rank; planes, tables, partials and
-// slots of their own
-static int tracers_on(ns_solver* s, const char* who) {
-    if (!s) { set_err("null solver"); return NS_EINVAL; }
-    if (!s->tr.on) { set_err("%s: tracers are not enabled (ns_tracers_enable)", who); return NS_EINVAL; }
-    return 0;
-}
-
-int ns_tracers_enable(ns_solver* s, int64_t capacity) {
-    if (!s) { set_err("null solver"); return NS_EINVAL; }
-    if (s->tr.on) { set_err("ns_tracers_enable: tracers are already enabled"); return NS_EINVAL; }
-    if (capacity <= 0) { set_err("ns_tracers_enable: capacity %lld is not positive", (long long)capacity); return NS_EINVAL; }
-    if (s->nranks > 1) {
-        set_err("ns_tracers_enable: nranks > 1 is not supported (particles would migrate between slabs)");
-        return NS_EINVAL;
-    }
-    HIPCHK(hipSetDevice(s->device));
-    using Q = ns_solver::Tracers;
-    auto& q = s->tr;
-    const nsg::Geo& g = s->g;
-    // the faces from the spacings the solver holds, summed one by one: xf[i + 1] = xf[i] + hx[i]
-    std::vector<double> hx(g.nx), hy(g.ny);
-    HIPCHK(hipMemcpy(hx.data(), s->c.hx, (size_t)g.nx * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(hy.data(), s->c.hy, (size_t)g.ny * sizeof(double), hipMemcpyDeviceToHost));
-    auto faces = [](const std::vector<double>& h, std::vector<double>& f) {
-        f.assign(h.size() + 1, 0.0);
-        for (size_t i = 0; i < h.size(); i++) f[i + 1] = f[i] + h[i];
-        for (double v : h)
-            if (v != h[0]) return 0.0;
-        return (double)h.size() / f.back();   // uniform: cells per unit length
-    };
-    const double rhx = faces(hx, q.xf), rhy = faces(hy, q.yf);
-    const size_t cap = (size_t)capacity;
-    CHK(dev_alloc(s, &q.mem, cap * (5 * sizeof(double) + sizeof(int32_t)), true, "tracer planes"));
-    std::vector<double> tab(q.xf);
-    tab.insert(tab.end(), q.yf.begin(), q.yf.end());
-    CHK(dev_upload(s, &q.tab, tab, "tracer face tables"));
-    CHK(dev_alloc(s, &q.part, (size_t)nsg::tracer_blocks(capacity) * 4 * sizeof(double), false, "tracer partials"));
-    CHK(dev_alloc(s, &q.scal, Q::NSLOT * sizeof(double), true, "tracer slots"));
-    if (hipHostMalloc(&q.hs, Q::NSLOT * sizeof(double), hipHostMallocDefault) != hipSuccess) { set_err("hipHostMalloc failed"); return NS_ENOMEM; }
-    nsg::TracerArgs& a = q.a;
-    a = nsg::TracerArgs{};
-    a.xf = q.tab;
-    a.yf = q.tab + g.nx + 1;
-    a.rhx = rhx;
-    a.rhy = rhy;
-    a.x = q.mem;
-    a.y = a.x + cap;
-    a.wu = a.y + cap;
-    a.wv = a.wu + cap;
-    a.age = a.wv + cap;
-    a.st = reinterpret_cast<int32_t*>(a.age + cap);
-    a.part = q.part;
-    // the edges a particle leaves the domain through (the rest are walls): per side on a rectangle, per edge on a mask
-    auto open_edge = [&](int e) { return s->eprof[e].type == NS_BC_NEUMANN || s->eprof[e].type == NS_BC_INLET_UNI; };
-    if (g.fc) {
-        for (int e = 0; e < (int)s->eprof.size() && e < nsg::MAX_EDGES; e++)
-            if (open_edge(e)) a.exitm |= 1u << e;
-    } else {
-        for (int k = 0; k < 4; k++)
-            if (open_edge(s->side_edge[k])) a.exitm |= 1u << k;
-    }
-    q.cap = capacity;
-    q.n = 0;
-    q.on = true;
-    return 0;
-}
-
-int ns_tracers_add(ns_solver* s, const double* x, const double* y, int64_t n) {
-    CHK(tracers_on(s, "ns_tracers_add"));
-    auto& q = s->tr;
-    if (n < 0 || (n > 0 && (!x || !y))) { set_err("ns_tracers_add: %lld seeds with a NULL coordinate array", (long long)n); return NS_EINVAL; }
-    if (n > q.cap - q.n) {
-        set_err("ns_tracers_add: %lld seeds on top of %lld exceed the capacity %lld", (long long)n, (long long)q.n, (long long)q.cap);
-        return NS_EINVAL;
-    }
-    const int nx = s->g.nx, ny = s->g.ny;
-    auto cell = [](const std::vector<double>& f, double v) {   // f[i] <= v < f[i + 1], or -1
-        if (!(v >= 0.0 && v < f.back())) return -1;
-        return (int)(std::upper_bound(f.begin(), f.end(), v) - f.begin()) - 1;
-    };
-    for (int64_t k = 0; k < n; k++) {
-        if (!std::isfinite(x[k]) || !std::isfinite(y[k])) {
-            set_err("ns_tracers_add: seed %lld (%g, %g) is not finite", (long long)k, x[k], y[k]);
-            return NS_EINVAL;
-        }
-        const int i = cell(q.xf, x[k]), j = cell(q.yf, y[k]);
-        if (i < 0 || i >= nx || j < 0 || j >= ny || (!s->cid.empty() && s->cid[(size_t)i * ny + j] < 0)) {
-            set_err("ns_tracers_add: seed %lld (%g, %g) is not in a domain cell", (long long)k, x[k], y[k]);
-            return NS_EINVAL;
-        }
-    }
-    if (n == 0) return 0;
-    HIPCHK(hipSetDevice(s->device));
-    const nsg::TracerArgs& a = q.a;
-    const size_t nb = (size_t)n * sizeof(double);
-    HIPCHK(hipMemcpyAsync(a.x + q.n, x, nb, hipMemcpyHostToDevice, s->st));
-    HIPCHK(hipMemcpyAsync(a.y + q.n, y, nb, hipMemcpyHostToDevice, s->st));
-    HIPCHK(hipMemsetAsync(a.wu + q.n, 0, nb, s->st));
-    HIPCHK(hipMemsetAsync(a.wv + q.n, 0, nb, s->st));
-    HIPCHK(hipMemsetAsync(a.age + q.n, 0, nb, s->st));
-    HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a.st + q.n), NS_TRACER_LIVE | 4, (size_t)n, s->st));   // (fresh)
-    HIPCHK(hipStreamSynchronize(s->st));   // (the caller owns x, y)
-    q.n += n;
-    return 0;
-}
-
-int ns_tracers_get(ns_solver* s, int64_t first, int64_t n, double* x, double* y, double* age, int32_t* state) {
-    CHK(tracers_on(s, "ns_tracers_get"));
-    auto& q = s->tr;
-    if (first < 0 || n < 0 || first > q.n || n > q.n - first) {
-        set_err("ns_tracers_get: the range [%lld, %lld) is outside [0, %lld)", (long long)first, (long long)(first + n), (long long)q.n);
-        return NS_EINVAL;
-    }
-    HIPCHK(hipSetDevice(s->device));
-    const nsg::TracerArgs& a = q.a;
-    const size_t nb = (size_t)n * sizeof(double);
-    if (n > 0) {
-        if (x) HIPCHK(hipMemcpyAsync(x, a.x + first, nb, hipMemcpyDeviceToHost, s->st));
-        if (y) HIPCHK(hipMemcpyAsync(y, a.y + first, nb, hipMemcpyDeviceToHost, s->st));
-        if (age) HIPCHK(hipMemcpyAsync(age, a.age + first, nb, hipMemcpyDeviceToHost, s->st));
-        if (state) HIPCHK(hipMemcpyAsync(state, a.st + first, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s->st));
-    }
-    HIPCHK(hipStreamSynchronize(s->st));
-    if (state)
-        for (int64_t k = 0; k < n; k++) state[k] &= 3;   // (without the fresh bit)
-    return 0;
-}
-
-int ns_tracers_sample(ns_solver* s, double* u, double* v) {
-    CHK(tracers_on(s, "ns_tracers_sample"));
-    CHK(materialize(s));
-    auto& q = s->tr;
-    if (q.n == 0) return 0;
-    HIPCHK(hipSetDevice(s->device));
-    nsg::set_compute_cus(s->compute_cus);
-    if (!q.smp) CHK(dev_alloc(s, &q.smp, (size_t)q.cap * 2 * sizeof(double), true, "tracer samples"));
-    q.a.g = s->g;
-    q.a.u = s->arr[NS_ARR_U];
-    q.a.v = s->arr[NS_ARR_V];
-    q.a.n = q.n;
-    q.a.su = q.smp;
-    q.a.sv = q.smp + q.cap;
-    if (nsg::launch_tracer(q.a, 0, s->st) < 0) { set_err("the tracer kernel's launch was refused"); return NS_EHIP; }
-    const size_t nb = (size_t)q.n * sizeof(double);
-    if (u) HIPCHK(hipMemcpyAsync(u, q.a.su, nb, hipMemcpyDeviceToHost, s->st));
-    if (v) HIPCHK(hipMemcpyAsync(v, q.a.sv, nb, hipMemcpyDeviceToHost, s->st));
-    HIPCHK(hipStreamSynchronize(s->st));
-    return 0;
-}
-
-int ns_tracers_advance(ns_solver* s, double dt, int32_t steps) {
-    CHK(tracers_on(s, "ns_tracers_advance"));
-    if (!std::isfinite(dt)) { set_err("ns_tracers_advance: dt = %g is not finite", dt); return NS_EINVAL; }
-    if (steps < 0) { set_err("ns_tracers_advance: steps = %d is negative", steps); return NS_EINVAL; }
-    CHK(materialize(s));
-    if (s->tr.n == 0 || steps == 0) return 0;
-    HIPCHK(hipSetDevice(s->device));
-    nsg::set_compute_cus(s->compute_cus);
-    (void)s->tm.drain(nsg::tbit(nsg::T_TRACER), nullptr);   // (an earlier advance's intervals nobody asked for)
-    for (int k = 0; k < steps; k++) CHK(tracer_advance(s, dt, k == steps - 1));
-    return 0;
-}
-
-int ns_tracers_reset(ns_solver* s) {
-    CHK(tracers_on(s, "ns_tracers_reset"));
-    HIPCHK(hipSetDevice(s->device));
-    s->tr.n = 0;
-    HIPCHK(hipMemsetAsync(s->tr.scal, 0, ns_solver::Tracers::NSLOT * sizeof(double), s->st));
-    (void)s->tm.drain(nsg::tbit(nsg::T_TRACER), nullptr);
-    return 0;
-}
-
-int ns_tracers_last(ns_solver* s, ns_tracer_stats* out) {
-    CHK(tracers_on(s, "ns_tracers_last"));
-    if (!out) { set_err("ns_tracers_last: out is NULL"); return NS_EINVAL; }
-    HIPCHK(hipSetDevice(s->device));
-    auto& q = s->tr;
-    HIPCHK(hipMemcpyAsync(q.hs, q.scal, ns_solver::Tracers::NSLOT * sizeof(double), hipMemcpyDeviceToHost, s->st));
-    HIPCHK(hipStreamSynchronize(s->st));
-    ns_tracer_stats r{};
-    TCHK(s->tm.drain(nsg::tbit(nsg::T_TRACER), nullptr, nullptr, nullptr, &r));
-    r.n = q.n;
-    r.live = (int64_t)q.hs[0];
-    r.exited = (int64_t)q.hs[1];
-    r.stuck = (int64_t)q.hs[2];
-    r.age_max = r.live > 0 ? -q.hs[3] : 0.0;
-    *out = r;
-    return 0;
-}
-
-// ---------------- running flow statistics ("Flow statistics"): the entry points.  One rank; planes and
-// partials of their own
-static int avg_on(ns_solver* s, const char* who) {
-    if (!s) { set_err("null solver"); return NS_EINVAL; }
-    if (!s->av.on) { set_err("%s: flow statistics are not enabled (ns_avg_enable)", who); return NS_EINVAL; }
-    return 0;
-}
-
-int ns_avg_enable(ns_solver* s, const ns_avg_desc* d) {
-    if (!s) { set_err("null solver"); return NS_EINVAL; }
-    if (!d) { set_err("ns_avg_enable: the descriptor is NULL"); return NS_EINVAL; }
-    if (s->av.on) { set_err("ns_avg_enable: flow statistics are already enabled"); return NS_EINVAL; }
-    if (d->every < 1) { set_err("ns_avg_enable: every = %d is less than 1", d->every); return NS_EINVAL; }
-    const int known = NS_AVG_SECOND | NS_AVG_PRESSURE | NS_AVG_SCALAR;
-    if (d->flags & ~known) { set_err("ns_avg_enable: unknown flag bits 0x%x", (unsigned)(d->flags & ~known)); return NS_EINVAL; }
-    if (s->nranks > 1) { set_err("ns_avg_enable: nranks > 1 is not supported (the pressure comes from ns_derive, one rank)"); return NS_EINVAL; }
-    if ((d->flags & NS_AVG_SCALAR) && !s->sc.on) {
-        set_err("ns_avg_enable: NS_AVG_SCALAR needs a scalar (ns_scalar_enable first)");
-        return NS_EINVAL;
-    }
-    HIPCHK(hipSetDevice(s->device));
-    auto& q = s->av;
-    const nsg::Geo& g = s->g;
-    const bool second = d->flags & NS_AVG_SECOND, has_p = d->flags & NS_AVG_PRESSURE, has_t = d->flags & NS_AVG_SCALAR;
-    // the planes kept, in the kernel's order: sources u, v, T, P; co-moments uu, vv, uv, TT, uT, vT, pp
-    int mean_of[4] = {NS_AVG_U, NS_AVG_V, -1, -1}, co_of[7] = {-1, -1, -1, -1, -1, -1, -1};
-    int nsrc = 2, nco = 0;
-    if (has_t) mean_of[nsrc++] = NS_AVG_T;
-    if (has_p) mean_of[nsrc++] = NS_AVG_P;
-    if (second) {
-        co_of[nco++] = NS_AVG_UU; co_of[nco++] = NS_AVG_VV; co_of[nco++] = NS_AVG_UV;
-        if (has_t) { co_of[nco++] = NS_AVG_TT; co_of[nco++] = NS_AVG_UT; co_of[nco++] = NS_AVG_VT; }
-        if (has_p) co_of[nco++] = NS_AVG_PP;
-    }
-    const size_t pl = (size_t)g.nxl * g.ld;
-    q.nplanes = (size_t)nsrc + nco;
-    int rc = dev_alloc(s, &q.mem, (q.nplanes + (has_p ? 1 : 0)) * pl * sizeof(double), true, "flow statistics planes");
-    if (!rc && has_p) rc = dev_alloc(s, &q.ppart, (size_t)nsg::derived_partials(g) * 9 * sizeof(double), false, "flow statistics partials");
-    if (rc) {
-        for (double** p : {&q.mem, &q.ppart}) {
-            if (*p) (void)hipFree(*p);
-            *p = nullptr;
-        }
-        return rc;
-    }
-    q.a = nsg::MomArgs{};
-    for (auto& p : q.plane) p = nullptr;
-    double* next = q.mem;
-    for (int k = 0; k < nsrc; k++, next += pl) q.plane[mean_of[k]] = q.a.mean[k] = next;
-    for (int k = 0; k < nco; k++, next += pl) q.plane[co_of[k]] = q.a.S[k] = next;
-    q.P = has_p ? next : nullptr;
-    q.a.nxl = g.nxl;
-    q.a.ny = g.ny;
-    q.a.ld = g.ld;
-    q.every = d->every;
-    q.flags = d->flags;
-    q.nsrc = nsrc;
-    q.n = q.steps = 0;
-    q.acc = ns_avg_stats{};
-    q.on = true;
-    return 0;
-}
-
-int ns_avg_reset(ns_solver* s) {
-    CHK(avg_on(s, "ns_avg_reset"));
-    HIPCHK(hipSetDevice(s->device));
-    auto& q = s->av;
-    HIPCHK(hipMemsetAsync(q.mem, 0, q.nplanes * (size_t)s->g.nxl * s->g.ld * sizeof(double), s->st));
-    q.n = q.steps = 0;
-    (void)s->tm.drain(nsg::tbit(nsg::T_AVG), nullptr);
-    q.acc = ns_avg_stats{};
-    return 0;
-}
-
-int ns_avg_sample(ns_solver* s) {
-    CHK(avg_on(s, "ns_avg_sample"));
-    CHK(materialize(s));
-    HIPCHK(hipSetDevice(s->device));
-    nsg::set_compute_cus(s->compute_cus);
-    return avg_sample(s);
-}
-
-int ns_avg_get(ns_solver* s, int which, double* plane) {
-    CHK(avg_on(s, "ns_avg_get"));
-    if (which < 0 || which >= NS_AVG_NUM) { set_err("ns_avg_get: unknown plane %d", which); return NS_EINVAL; }
-    auto& q = s->av;
-    if (!q.plane[which]) {
-        set_err("ns_avg_get: plane %d is not accumulated by this solver (ns_avg_enable's flags 0x%x)", which, (unsigned)q.flags);
-        return NS_EINVAL;
-    }
-    if (!plane) { set_err("ns_avg_get: the output plane is NULL"); return NS_EINVAL; }
-    HIPCHK(hipSetDevice(s->device));
-    const nsg::Geo& g = s->g;
-    const size_t cells = (size_t)g.nxl * g.ny;
-    if (q.n == 0) {   // (nothing sampled: every plane is 0, and there is no 1 / n)
-        HIPCHK(hipStreamSynchronize(s->st));
-        std::fill(plane, plane + cells, 0.0);
-        return 0;
-    }
-    HIPCHK(hipMemcpy2DAsync(plane, (size_t)g.ny * 8, q.plane[which], (size_t)g.ld * 8, (size_t)g.ny * 8, g.nxl,
-                            hipMemcpyDeviceToHost, s->st));
-    HIPCHK(hipStreamSynchronize(s->st));
-    if (which >= NS_AVG_UU) {   // the population covariance S / n: one multiplication by the host-formed 1 / n
-        const double rn = 1.0 / (double)q.n;
-        for (size_t k = 0; k < cells; k++) plane[k] *= rn;
-    }
-    return 0;
-}
-
-int ns_avg_last(ns_solver* s, ns_avg_stats* out) {
-    CHK(avg_on(s, "ns_avg_last"));
-    if (!out) { set_err("ns_avg_last: out is NULL"); return NS_EINVAL; }
-    HIPCHK(hipSetDevice(s->device));
-    auto& q = s->av;
-    HIPCHK(hipStreamSynchronize(s->st));
-    TCHK(s->tm.drain(nsg::tbit(nsg::T_AVG), nullptr, nullptr, nullptr, nullptr, &q.acc));
-    ns_avg_stats r = q.acc;
-    q.acc = ns_avg_stats{};
-    r.n = q.n;
-    r.steps = q.steps;
-    *out = r;
-    return 0;
-}
-
-// ---------------- wall loads ("Wall loads"): the entry points.  One rank; buffers of their own
-static int loads_on(ns_solver* s, const char* who) {
-    if (!s) { set_err("null solver"); return NS_EINVAL; }
-    if (!s->lo.on) { set_err("%s: wall loads are not enabled (ns_loads_enable)", who); return NS_EINVAL; }
-    return 0;
-}
-static int loads_edge(ns_solver* s, const char* who, int32_t edge) {
-    CHK(loads_on(s, who));
-    if (edge < 0 || edge >= s->n_edges) { set_err("%s: edge %d of a grid with %d edges", who, edge, s->n_edges); return NS_EINVAL; }
-    return 0;
-}
-
-int ns_loads_enable(ns_solver* s, const ns_load_desc* d) {
-    if (!s) { set_err("null solver"); return NS_EINVAL; }
-    if (!d) { set_err("ns_loads_enable: the descriptor is NULL"); return NS_EINVAL; }
-    if (s->lo.on) { set_err("ns_loads_enable: wall loads are already enabled"); return NS_EINVAL; }
-    if (d->every < 1) { set_err("ns_loads_enable: every = %d is less than 1", d->every); return NS_EINVAL; }
-    if (d->capacity < 1) { set_err("ns_loads_enable: capacity = %d is less than 1", d->capacity); return NS_EINVAL; }
-    if (s->nranks > 1) { set_err("ns_loads_enable: nranks > 1 is not supported (the pressure comes from ns_derive, one rank)"); return NS_EINVAL; }
-    HIPCHK(hipSetDevice(s->device));
-    auto& q = s->lo;
-    const nsg::Geo& g = s->g;
-    std::vector<double> hx(g.nx), hy(g.ny);
-    HIPCHK(hipMemcpy(hx.data(), s->c.hx, (size_t)g.nx * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(hy.data(), s->c.hy, (size_t)g.ny * sizeof(double), hipMemcpyDeviceToHost));
-    // the topology as the kernels see it: a rectangle's sides, or the masked domain's code plane
-    std::vector<int32_t> fc;
-    if (g.fc) {
-        fc.resize((size_t)g.nxl * g.ld);
-        HIPCHK(hipMemcpy(fc.data(), g.fc, fc.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    }
-    auto inside = [&](int i, int j) { return fc.empty() || (fc[(size_t)i * g.ld + j] & nsg::FC_IN) != 0; };
-    auto edge_of = [&](int i, int j, int k) {
-        if (fc.empty()) {
-            const bool bnd = k == 0 ? i == 0 : k == 1 ? i == g.nx - 1 : k == 2 ? j == 0 : j == g.ny - 1;
-            return bnd ? s->side_edge[k] : -1;
-        }
-        const int e = nsg::fc_edge(fc[(size_t)i * g.ld + j], k);
-        return e == nsg::FC_INT ? -1 : e;
-    };
-    nsg::LoadList L;
-    if (!nsg::build_load_list(g.nx, g.ny, g.ld, s->n_edges, hx.data(), hy.data(), inside, edge_of, L) || L.face.empty()) {
-        set_err("ns_loads_enable: the boundary-face list could not be built");
-        return NS_EINVAL;
-    }
-    const size_t nf = L.face.size(), nch = L.chunk.size(), nrec = (size_t)s->n_edges * NS_LOAD_NUM;
-    // one table block: faces | chunks (16 bytes each) | the edges' chunk offsets
-    std::vector<int32_t> tab(4 * (nf + nch) + L.cs.size());
-    std::memcpy(tab.data(), L.face.data(), nf * sizeof(nsg::LoadFace));
-    std::memcpy(tab.data() + 4 * nf, L.chunk.data(), nch * sizeof(nsg::LoadChunk));
-    std::memcpy(tab.data() + 4 * (nf + nch), L.cs.data(), L.cs.size() * sizeof(int32_t));
-    int rc = dev_upload(s, &q.tab, tab, "wall-load tables");
-    if (!rc) rc = dev_alloc(s, &q.val, 6 * nf * sizeof(double), true, "wall-load face values");
-    if (!rc) rc = dev_alloc(s, &q.part, nch * NS_LOAD_NUM * sizeof(double), true, "wall-load partials");
-    if (!rc) rc = dev_alloc(s, &q.ring, ((size_t)d->capacity + 1) * nrec * sizeof(double), true, "wall-load records");
-    if (rc) {
-        for (double** p : {&q.val, &q.part, &q.ring}) {
-            if (*p) (void)hipFree(*p);
-            *p = nullptr;
-        }
-        if (q.tab) (void)hipFree(q.tab);
-        q.tab = nullptr;
-        return rc;
-    }
-    q.a = nsg::LoadArgs{};
-    q.a.face = reinterpret_cast<const nsg::LoadFace*>(q.tab);
-    q.a.chunk = reinterpret_cast<const nsg::LoadChunk*>(q.tab + 4 * nf);
-    q.a.cs = q.tab + 4 * (nf + nch);
-    q.a.val = q.val;
-    q.a.part = q.part;
-    q.a.nf = (int)nf;
-    q.a.nchunk = (int)nch;
-    q.a.n_edges = s->n_edges;
-    q.list = std::move(L);
-    q.every = d->every;
-    q.capacity = d->capacity;
-    q.nrec = (int)nrec;
-    q.rstep.assign((size_t)d->capacity, 0);
-    q.total = q.steps = 0;
-    q.acc = ns_load_stats{};
-    q.on = true;
-    return 0;
-}
-
-int ns_loads_reset(ns_solver* s) {
-    CHK(loads_on(s, "ns_loads_reset"));
-    auto& q = s->lo;
-    q.total = q.steps = 0;
-    (void)s->tm.drain(nsg::tbit(nsg::T_LOADS), nullptr);
-    q.acc = ns_load_stats{};
-    return 0;
-}
-
-int ns_loads_sample(ns_solver* s) {
-    CHK(loads_on(s, "ns_loads_sample"));
-    CHK(materialize(s));
-    HIPCHK(hipSetDevice(s->device));
-    nsg::set_compute_cus(s->compute_cus);
-    return loads_sample(s, -1);
-}
-
-int ns_loads_edges(ns_solver* s, double* out) {
-    CHK(loads_on(s, "ns_loads_edges"));
-    if (!out) { set_err("ns_loads_edges: out is NULL"); return NS_EINVAL; }
-    CHK(materialize(s));
-    HIPCHK(hipSetDevice(s->device));
-    nsg::set_compute_cus(s->compute_cus);
-    auto& q = s->lo;
-    double* rec = q.ring + (size_t)q.capacity * q.nrec;   // (the record behind the ring)
-    CHK(loads_run(s, rec, false));
-    HIPCHK(hipMemcpyAsync(out, rec, (size_t)q.nrec * sizeof(double), hipMemcpyDeviceToHost, s->st));
-    HIPCHK(hipStreamSynchronize(s->st));
-    return 0;
-}
-
-int ns_loads_face_count(ns_solver* s, int32_t edge, int64_t* n) {
-    CHK(loads_edge(s, "ns_loads_face_count", edge));
-    if (!n) { set_err("ns_loads_face_count: n is NULL"); return NS_EINVAL; }
-    *n = s->lo.list.fs[edge + 1] - s->lo.list.fs[edge];
-    return 0;
-}
-
-int ns_loads_faces(ns_solver* s, int32_t edge, const ns_load_faces* out) {
-    CHK(loads_edge(s, "ns_loads_faces", edge));
-    if (!out) { set_err("ns_loads_faces: out is NULL"); return NS_EINVAL; }
-    CHK(materialize(s));
-    HIPCHK(hipSetDevice(s->device));
-    nsg::set_compute_cus(s->compute_cus);
-    auto& q = s->lo;
-    const size_t f0 = (size_t)q.list.fs[edge], n = (size_t)q.list.fs[edge + 1] - f0, nf = q.list.face.size();
-    if (out->s) std::copy(q.list.s.begin() + f0, q.list.s.begin() + f0 + n, out->s);
-    if (out->ds) std::copy(q.list.ds.begin() + f0, q.list.ds.begin() + f0 + n, out->ds);
-    double* const dst[6] = {out->p, out->tx, out->ty, out->un, out->tb, out->qn};
-    if (n == 0 || std::all_of(dst, dst + 6, [](double* p) { return !p; })) return 0;
-    CHK(loads_run(s, nullptr, false));
-    for (int k = 0; k < 6; k++)
-        if (dst[k]) HIPCHK(hipMemcpyAsync(dst[k], q.val + k * nf + f0, n * sizeof(double), hipMemcpyDeviceToHost, s->st));
-    HIPCHK(hipStreamSynchronize(s->st));
-    return 0;
-}
-
-int ns_loads_history(ns_solver* s, int64_t first, int64_t n, int64_t* step, double* rec) {
-    CHK(loads_on(s, "ns_loads_history"));
-    auto& q = s->lo;
-    const int64_t held = std::min<int64_t>(q.total, q.capacity);
-    if (first < 0 || n < 0 || first > held || n > held - first) {
-        set_err("ns_loads_history: the range [%lld, %lld) is outside [0, %lld)", (long long)first, (long long)(first + n), (long long)held);
-        return NS_EINVAL;
-    }
-    HIPCHK(hipSetDevice(s->device));
-    const int64_t oldest = q.total - held;   // (sample number of the oldest record held; its slot: % capacity)
-    for (int64_t k = 0; k < n; k++) {
-        const int64_t slot = (oldest + first + k) % q.capacity;
-        if (step) step[k] = q.rstep[slot];
-        if (rec)
-            HIPCHK(hipMemcpyAsync(rec + (size_t)k * q.nrec, q.ring + (size_t)slot * q.nrec, (size_t)q.nrec * sizeof(double),
-                                  hipMemcpyDeviceToHost, s->st));
-    }
-    HIPCHK(hipStreamSynchronize(s->st));
-    return 0;
-}
-
-int ns_loads_last(ns_solver* s, ns_load_stats* out) {
-    CHK(loads_on(s, "ns_loads_last"));
-    if (!out) { set_err("ns_loads_last: out is NULL"); return NS_EINVAL; }
-    HIPCHK(hipSetDevice(s->device));
-    auto& q = s->lo;
-    HIPCHK(hipStreamSynchronize(s->st));
-    TCHK(s->tm.drain(nsg::tbit(nsg::T_LOADS), nullptr, nullptr, nullptr, nullptr, nullptr, &q.acc));
-    ns_load_stats r = q.acc;
-    q.acc = ns_load_stats{};
-    r.total = q.total;
-    r.held = std::min<int64_t>(q.total, q.capacity);
-    r.steps = q.steps;
-    *out = r;
     return 0;
 }
 
@@ -5323,11 +4250,7 @@ int ns_kernel(ns_solver* s, int which, int iters, double* out) {
 
 // ---- passive scalar
 static int scalar_check(ns_solver* s, const char* who) {
-    if (!s) { set_err("null solver"); return NS_EINVAL; }
-    if (!s->sc.on) { set_err("%s: no scalar enabled (ns_scalar_enable)", who); return NS_EINVAL; }
-    HIPCHK(hipSetDevice(s->device));
-    nsg::set_compute_cus(s->compute_cus);
-    return 0;
+    return enter(s, who, s && s->sc.on, "no scalar enabled", "ns_scalar_enable", LAUNCH);
 }
 
 int ns_scalar_enable(ns_solver* s, const ns_scalar_desc* d) {
@@ -5346,7 +4269,7 @@ int ns_scalar_enable(ns_solver* s, const ns_scalar_desc* d) {
             return NS_EINVAL;
         }
     HIPCHK(hipSetDevice(s->device));
-    auto& q = s->sc;
+    ns_solver::Scalar q;
     const nsg::Geo& g = s->g;
     q.pe = d->pe;
     for (int k = 0; k < 4; k++) {
@@ -5359,34 +4282,28 @@ int ns_scalar_enable(ns_solver* s, const ns_scalar_desc* d) {
         q.omega = 2.0 / (1.0 + std::sqrt(1.0 - rho * rho));
     }
     // the Helmholtz tables' Dirichlet-face terms 2 / h^2 on the scalar's Dirichlet sides (coef_tables' bx / by)
-    std::vector<double> hx(g.nx), hy(g.ny), bxy((size_t)g.nx + g.ny, 0.0);
-    HIPCHK(hipMemcpy(hx.data(), s->c.hx, g.nx * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(hy.data(), s->c.hy, g.ny * sizeof(double), hipMemcpyDeviceToHost));
+    std::vector<double> hx, hy, bxy((size_t)g.nx + g.ny, 0.0);
+    CHK(host_spacings(s, hx, hy));
     if (!q.neu[0]) bxy[0] += 2.0 / (hx[0] * hx[0]);
     if (!q.neu[1]) bxy[g.nx - 1] += 2.0 / (hx[g.nx - 1] * hx[g.nx - 1]);
     if (!q.neu[2]) bxy[g.nx] += 2.0 / (hy[0] * hy[0]);
     if (!q.neu[3]) bxy[g.nx + g.ny - 1] += 2.0 / (hy[g.ny - 1] * hy[g.ny - 1]);
     const int np = nsg::max_partials(g);
-    int rc = dev_upload(s, &q.bxy, bxy, "scalar tables");
-    if (!rc) rc = dev_alloc(s, &q.mem, 4 * s->plane * sizeof(double), true, "scalar planes");
-    if (!rc) rc = dev_alloc(s, &q.part, (size_t)np * 8 * sizeof(double), false, "scalar partials");
-    if (!rc) rc = dev_alloc(s, &q.scal, ns_solver::Scalar::NSLOT * sizeof(double), true, "scalar slots");
-    if (!rc && hipHostMalloc(&q.hs, ns_solver::Scalar::NSLOT * sizeof(double), hipHostMallocDefault) != hipSuccess) {
-        set_err("hipHostMalloc failed");
-        rc = NS_ENOMEM;
-    }
-    if (!rc && hipEventCreateWithFlags(&q.ev, hipEventDisableTiming) != hipSuccess) { set_err("event create failed"); rc = NS_EHIP; }
-    if (!rc && hipStreamSynchronize(s->st) != hipSuccess) { set_err("stream sync failed"); rc = NS_EHIP; }
-    if (rc) {
-        scalar_free(s);
-        return rc;
-    }
-    double* p0 = q.mem + (size_t)s->hp * g.ld;
+    CHK(dev_upload(s, q.bxy, bxy, "scalar tables"));
+    CHK(dev_alloc(s, q.mem, 4 * s->plane * sizeof(double), true, "scalar planes"));
+    CHK(dev_alloc(s, q.part, (size_t)np * 8 * sizeof(double), false, "scalar partials"));
+    CHK(dev_alloc(s, q.scal, ns_solver::Scalar::NSLOT * sizeof(double), true, "scalar slots"));
+    CHK(pinned_alloc(q.hs, ns_solver::Scalar::NSLOT));
+    if (hipStreamSynchronize(s->st) != hipSuccess) { set_err("stream sync failed"); return NS_EHIP; }
+    // (the event last: the one thing here without an owner)
+    if (hipEventCreateWithFlags(&q.ev, hipEventDisableTiming) != hipSuccess) { set_err("event create failed"); return NS_EHIP; }
+    double* p0 = q.mem.get() + (size_t)s->hp * g.ld;
     q.T = p0; q.TT = p0 + s->plane; q.R = p0 + 2 * s->plane; q.C = p0 + 3 * s->plane;
     q.ct = s->c;
-    q.ct.bx = q.bxy;
-    q.ct.by = q.bxy + g.nx;
+    q.ct.bx = q.bxy.get();
+    q.ct.by = q.ct.bx + g.nx;
     q.on = true;
+    s->sc = std::move(q);
     return 0;
 }
 
@@ -5433,16 +4350,16 @@ int ns_scalar_kernel(ns_solver* s, int which, double* out) {
     auto& q = s->sc;
     if (which == 1) {
         CHK(scalar_rhs(s));
-        HIPCHK(hipMemcpyAsync(q.hs, q.scal, S::NSLOT * sizeof(double), hipMemcpyDeviceToHost, s->st));
+        HIPCHK(hipMemcpyAsync(q.hs.get(), q.scal.get(), S::NSLOT * sizeof(double), hipMemcpyDeviceToHost, s->st));
         HIPCHK(hipStreamSynchronize(s->st));
         if (out) out[0] = q.hs[S::BN2];
         return 0;
     }
     if (which == 2) {
         // ||rT||^2 of the plane as it stands, then batches from the current T
-        const int nb = nsg::launch_sums(s->g, q.R, q.part, s->st);
-        nsg::launch_reduce_sum(q.part, nb, 2, q.scal + S::AUX, s->st);
-        HIPCHK(hipMemcpyAsync(q.scal + S::BN2, q.scal + S::AUX + 1, sizeof(double), hipMemcpyDeviceToDevice, s->st));
+        const int nb = nsg::launch_sums(s->g, q.R, q.part.get(), s->st);
+        nsg::launch_reduce_sum(q.part.get(), nb, 2, q.scal.get() + S::AUX, s->st);
+        HIPCHK(hipMemcpyAsync(q.scal.get() + S::BN2, q.scal.get() + S::AUX + 1, sizeof(double), hipMemcpyDeviceToDevice, s->st));
         q.sweeps = 0;
         CHK(scalar_batch(s, q.next));
         CHK(scalar_wait(s));
@@ -5458,11 +4375,11 @@ int ns_scalar_kernel(ns_solver* s, int which, double* out) {
         const bool forced[2] = {fx, fy};
         for (int k = 0; k < 2; k++) {
             if (forced[k]) continue;
-            const int nb = nsg::launch_sums(s->g, s->arr[comp[k]], q.part, s->st);
-            nsg::launch_reduce_sum(q.part, nb, 2, q.scal + S::AUX, s->st);
-            HIPCHK(hipMemcpyAsync(s->scal + S_HBN + k, q.scal + S::AUX + 1, sizeof(double), hipMemcpyDeviceToDevice, s->st));
+            const int nb = nsg::launch_sums(s->g, s->arr[comp[k]], q.part.get(), s->st);
+            nsg::launch_reduce_sum(q.part.get(), nb, 2, q.scal.get() + S::AUX, s->st);
+            HIPCHK(hipMemcpyAsync(s->scal + S_HBN + k, q.scal.get() + S::AUX + 1, sizeof(double), hipMemcpyDeviceToDevice, s->st));
         }
-        HIPCHK(hipMemcpyAsync(q.hs, q.scal, S::NSLOT * sizeof(double), hipMemcpyDeviceToHost, s->st));
+        HIPCHK(hipMemcpyAsync(q.hs.get(), q.scal.get(), S::NSLOT * sizeof(double), hipMemcpyDeviceToHost, s->st));
         CHK(fetch(s));
         if (out) { out[0] = q.hs[S::BN2]; out[1] = s->hs[S_HBN]; out[2] = s->hs[S_HBN + 1]; }
         return 0;
@@ -5539,7 +4456,7 @@ int ns_time_poisson(ns_solver* s, int warmup, int iters, double* out) {
     if (s->kv[0]) { set_err("ns_time_poisson times the rectangle's sweeps (no NEUMANN side, no mask)"); return NS_EINVAL; }
     HIPCHK(hipSetDevice(s->device));
     nsg::set_compute_cus(s->compute_cus);
-    (void)s->tm.drain(nsg::tbit(nsg::T_RAW), nullptr);   // (a failed call's leftovers)
+    (void)s->tm.drop(nsg::tbit(nsg::T_RAW));   // (a failed call's leftovers)
     // NSGPU_TIME_PAIRS=1: time the two-sweep (temporally blocked) pass instead of a single sweep
     const bool pairs = s->k.time_pairs && s->poisson != NS_POISSON_JACOBI;
     auto one = [&](double* part) -> int {
@@ -5575,7 +4492,7 @@ int ns_time_poisson_fp32(ns_solver* s, int warmup, int iters, double* out) {
     if (s->kv[0]) { set_err("ns_time_poisson_fp32 times the rectangle's sweeps (no NEUMANN side, no mask)"); return NS_EINVAL; }
     HIPCHK(hipSetDevice(s->device));
     nsg::set_compute_cus(s->compute_cus);
-    (void)s->tm.drain(nsg::tbit(nsg::T_RAW), nullptr);   // (a failed call's leftovers)
+    (void)s->tm.drop(nsg::tbit(nsg::T_RAW));   // (a failed call's leftovers)
     CHK(to_f32(s));
     int nb = 0;
     for (int k = 0; k < warmup; k++) CHK(pois_sweep32(s, nullptr, &nb));

@@ -1,8 +1,8 @@
 // ns_timing.h -- the one recorder of the step's kernel timings (host side; ns_solver owns one as `tm`).
 //
 // A timed call is an INTERVAL of a kind: opened before the call, closed after it, and later DRAINED by kind into
-// the stats line of that kind (one table row per kind, below).  Two modes, as ever: the dispatch-stamped single
-// launch (`stamped`: one rank with k.ext_timing -- the next launch goes through hipExtLaunchKernel, which stamps
+// the stats line of that kind (one row per kind, in the table of the struct that owns it, below).  Two modes, as
+// ever: the dispatch-stamped single launch (`stamped`: one rank with k.ext_timing -- the next launch goes through hipExtLaunchKernel, which stamps
 // the interval's events at the kernel's own begin and end; no launch = an empty interval) and marker events
 // around the call, which also count the dispatch latency (slabs, NSGPU_EXT_TIMING=0, and the sites that ask for
 // them: several launches or a library call in one interval).  Events are created on demand and reused.
@@ -11,6 +11,7 @@
 // Api: the event calls (nsg::HipTiming in ns_internal.h; a stub in tests/timing_host_test.cpp).  Every int returned
 // here is the Api's error code, 0 = success.
 #pragma once
+#include <array>
 #include <cstdint>
 #include <vector>
 
@@ -25,45 +26,55 @@ constexpr unsigned tbit(TKind k) { return 1u << k; }
 constexpr unsigned T_MG = tbit(T_SWEEP) | tbit(T_RESTRICT) | tbit(T_CYCLE) | tbit(T_GUESS);
 constexpr unsigned T_FPS = tbit(T_FPS_DCT) | tbit(T_FPS_TRI) | tbit(T_FPS_IDCT);
 
-// kind -> (elapsed ms, weighted count) of ns_stats, of ns_scalar_stats, of ns_derived_stats, of ns_tracer_stats, of
-// ns_avg_stats or of ns_load_stats.  A new timed line: one enum value, one row
-struct TLine {
-    double ns_stats::*t;
-    int32_t ns_stats::*n;
-    double ns_scalar_stats::*st;
-    int32_t ns_scalar_stats::*sn;
-    double ns_derived_stats::*dt = nullptr;
-    int32_t ns_derived_stats::*dn = nullptr;
-    double ns_tracer_stats::*pt = nullptr;
-    int32_t ns_tracer_stats::*pn = nullptr;
-    double ns_avg_stats::*at = nullptr;
-    int32_t ns_avg_stats::*an = nullptr;
-    double ns_load_stats::*lt = nullptr;
-    int32_t ns_load_stats::*ln = nullptr;
+// one row per kind: the kind's (elapsed ms, weighted count) fields in the stats struct S that owns it; trows<S>() is
+// S's table.  Every kind but T_RAW has exactly one owner (checked below).  A new timed line for a new struct: one enum
+// value, one trows<> table beside these and the struct's name in the check's list -- no edit to Timing
+template <class S>
+struct TRow {
+    TKind kind;
+    double S::*t;
+    int32_t S::*n;   // null: the line shares another's count
 };
-inline const TLine& tline(TKind k) {
-    static const TLine tab[T_NKIND] = {
-        {&ns_stats::t_poisson_kernel_ms, &ns_stats::n_poisson_kernels, nullptr, nullptr},    // T_SWEEP
-        {&ns_stats::t_restrict_kernel_ms, &ns_stats::n_restrict_kernels, nullptr, nullptr},  // T_RESTRICT
-        {&ns_stats::t_cycle_kernel_ms, &ns_stats::n_cycle_kernels, nullptr, nullptr},        // T_CYCLE
-        {&ns_stats::t_guess_kernel_ms, &ns_stats::n_guess_kernels, nullptr, nullptr},        // T_GUESS
-        {&ns_stats::t_helm_kernel_ms, &ns_stats::n_helm_kernels, nullptr, nullptr},          // T_HELM
-        {&ns_stats::t_rhs_kernel_ms, &ns_stats::n_rhs_kernels, nullptr, nullptr},            // T_K1
-        {&ns_stats::t_band_kernel_ms, &ns_stats::n_band_kernels, nullptr, nullptr},          // T_BAND
-        {&ns_stats::t_k5_kernel_ms, &ns_stats::n_k5_kernels, nullptr, nullptr},              // T_K5
+template <class S, size_t N>
+using TRows = std::array<TRow<S>, N>;
+template <class S>
+constexpr auto trows() = delete;   // (a struct without a table owns no kind: it cannot be drained into)
+template <> constexpr auto trows<ns_stats>() {
+    return TRows<ns_stats, 11>{{
+        {T_SWEEP, &ns_stats::t_poisson_kernel_ms, &ns_stats::n_poisson_kernels},
+        {T_RESTRICT, &ns_stats::t_restrict_kernel_ms, &ns_stats::n_restrict_kernels},
+        {T_CYCLE, &ns_stats::t_cycle_kernel_ms, &ns_stats::n_cycle_kernels},
+        {T_GUESS, &ns_stats::t_guess_kernel_ms, &ns_stats::n_guess_kernels},
+        {T_HELM, &ns_stats::t_helm_kernel_ms, &ns_stats::n_helm_kernels},
+        {T_K1, &ns_stats::t_rhs_kernel_ms, &ns_stats::n_rhs_kernels},
+        {T_BAND, &ns_stats::t_band_kernel_ms, &ns_stats::n_band_kernels},
+        {T_K5, &ns_stats::t_k5_kernel_ms, &ns_stats::n_k5_kernels},
         // the direct solve's three phases share n_fps_solves: the recurrences, which every solve has, count it
-        {&ns_stats::t_fps_dct_ms, nullptr, nullptr, nullptr},                                // T_FPS_DCT
-        {&ns_stats::t_fps_tri_ms, &ns_stats::n_fps_solves, nullptr, nullptr},                // T_FPS_TRI
-        {&ns_stats::t_fps_idct_ms, nullptr, nullptr, nullptr},                               // T_FPS_IDCT
-        {nullptr, nullptr, &ns_scalar_stats::t_rhs_kernel_ms, &ns_scalar_stats::n_rhs_kernels},   // T_SCALAR_RHS
-        {nullptr, nullptr, nullptr, nullptr, &ns_derived_stats::t_kernel_ms, &ns_derived_stats::n_kernels},   // T_DERIVED
-        {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &ns_tracer_stats::t_kernel_ms, &ns_tracer_stats::n_kernels},   // T_TRACER
-        {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &ns_avg_stats::t_kernel_ms, &ns_avg_stats::n_kernels},   // T_AVG
-        {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &ns_load_stats::t_kernel_ms, &ns_load_stats::n_kernels},   // T_LOADS
-        {nullptr, nullptr, nullptr, nullptr},                                                // T_RAW
-    };
-    return tab[k];
+        {T_FPS_DCT, &ns_stats::t_fps_dct_ms, nullptr},
+        {T_FPS_TRI, &ns_stats::t_fps_tri_ms, &ns_stats::n_fps_solves},
+        {T_FPS_IDCT, &ns_stats::t_fps_idct_ms, nullptr},
+    }};
 }
+template <> constexpr auto trows<ns_scalar_stats>() { return TRows<ns_scalar_stats, 1>{{{T_SCALAR_RHS, &ns_scalar_stats::t_rhs_kernel_ms, &ns_scalar_stats::n_rhs_kernels}}}; }
+template <> constexpr auto trows<ns_derived_stats>() { return TRows<ns_derived_stats, 1>{{{T_DERIVED, &ns_derived_stats::t_kernel_ms, &ns_derived_stats::n_kernels}}}; }
+template <> constexpr auto trows<ns_tracer_stats>() { return TRows<ns_tracer_stats, 1>{{{T_TRACER, &ns_tracer_stats::t_kernel_ms, &ns_tracer_stats::n_kernels}}}; }
+template <> constexpr auto trows<ns_avg_stats>() { return TRows<ns_avg_stats, 1>{{{T_AVG, &ns_avg_stats::t_kernel_ms, &ns_avg_stats::n_kernels}}}; }
+template <> constexpr auto trows<ns_load_stats>() { return TRows<ns_load_stats, 1>{{{T_LOADS, &ns_load_stats::t_kernel_ms, &ns_load_stats::n_kernels}}}; }
+
+// the kinds S owns, as a mask of tbit
+template <class S>
+constexpr unsigned towned() {
+    unsigned m = 0;
+    for (const TRow<S>& r : trows<S>()) m |= tbit(r.kind);
+    return m;
+}
+// as many rows as kinds, and every kind but T_RAW in some row: each has exactly one owner
+template <class... S>
+constexpr bool one_owner_each() {
+    return (trows<S>().size() + ...) == T_NKIND - 1 && (towned<S>() | ...) == (tbit(T_NKIND) - 1u) - tbit(T_RAW);
+}
+static_assert(one_owner_each<ns_stats, ns_scalar_stats, ns_derived_stats, ns_tracer_stats, ns_avg_stats, ns_load_stats>(),
+              "a timed kind without an owner, or with two");
 
 template <class Api>
 class Timing {
@@ -150,30 +161,26 @@ public:
         return 0;
     }
 
-    // add the closed intervals of `kinds` (a mask of tbit) to the stats (any may be null: those figures are
-    // dropped) and release them.  The caller knows the stream has passed them
-    int drain(unsigned kinds, ns_stats* st, ns_scalar_stats* sc = nullptr, ns_derived_stats* dv = nullptr,
-              ns_tracer_stats* tr = nullptr, ns_avg_stats* av = nullptr, ns_load_stats* lo = nullptr) {
+    // release the closed intervals of `kinds` (a mask of tbit); those whose kind S owns are first added, in interval
+    // order, to their line of *st (null: nobody's figures -- drop).  The caller knows the stream has passed them
+    template <class S>
+    int drain(unsigned kinds, S* st) {
         int err = 0;
         for (size_t i = 0; i < iv_.size(); i++) {
             Iv& v = iv_[i];
             if (v.state != CLOSED || !(kinds >> v.kind & 1)) continue;
-            const TLine& L = tline(v.kind);
-            float ms = 0.f;
-            if ((st && L.t) || (sc && L.st) || (dv && L.dt) || (tr && L.pt) || (av && L.at) || (lo && L.lt)) {
+            for (const TRow<S>& r : trows<S>()) {
+                if (!st || r.kind != v.kind) continue;
+                float ms = 0.f;
                 const int e = Api::elapsed(&ms, v.a, v.b);
                 if (e && !err) err = e;
-                if (!e && st && L.t) { st->*L.t += ms; if (L.n) st->*L.n += v.weight; }
-                if (!e && sc && L.st) { sc->*L.st += ms; sc->*L.sn += v.weight; }
-                if (!e && dv && L.dt) { dv->*L.dt += ms; dv->*L.dn += v.weight; }
-                if (!e && tr && L.pt) { tr->*L.pt += ms; tr->*L.pn += v.weight; }
-                if (!e && av && L.at) { av->*L.at += ms; av->*L.an += v.weight; }
-                if (!e && lo && L.lt) { lo->*L.lt += ms; lo->*L.ln += v.weight; }
+                if (!e) { st->*r.t += ms; if (r.n) st->*r.n += v.weight; }
             }
             release((int)i);
         }
         return err;
     }
+    int drop(unsigned kinds) { return drain<ns_stats>(kinds, nullptr); }
 
     // the T_RAW intervals: the sum of their times, and the span from the first one's start to the last one's end
     int drain_raw(double* total_ms, double* span_ms) {
@@ -191,7 +198,7 @@ public:
         float span = 0.f;
         if (first >= 0 && !err) err = Api::elapsed(&span, iv_[first].a, iv_[last].b);
         *span_ms = span;
-        (void)drain(tbit(T_RAW), nullptr);
+        (void)drop(tbit(T_RAW));
         return err;
     }
 

@@ -2,7 +2,8 @@
 tests/fps_tables_host_test.cpp builds them for the operators of tests/test_gpu_fps_setup_bits.py that need none -- every
 square, lx and x-stretched shape, the outflow channel, the 2- and 3-rank splits -- as a stand-alone program under the
 sanitizers, and checks the table sizes, a slab's rows against the one-rank table's, the block fixed points, what an
-outflow side changes and the pivot-shortcut census.  And how ns_solver.cpp uses the header."""
+outflow side changes and the pivot-shortcut census.  And how the solver (ns_solver.h, ns_solver.cpp, ns_observe.cpp)
+uses the header."""
 import os
 import re
 import subprocess
@@ -22,7 +23,9 @@ def test_fps_tables_host_program_under_sanitizers(tmp_path):
 
 
 def test_solver_takes_its_pivots_from_the_header_and_its_layout_from_one_list():
-    src = open(os.path.join(CSRC, "ns_solver.cpp")).read()
+    cpp = open(os.path.join(CSRC, "ns_solver.cpp")).read()
+    sh = open(os.path.join(CSRC, "ns_solver.h")).read()   # (the solver's struct and what ns_observe.cpp shares)
+    src = sh + cpp + open(os.path.join(CSRC, "ns_observe.cpp")).read()
     hdr = open(os.path.join(CSRC, "ns_fps_tables.h")).read()
     # Thomas' pivot recurrence is written once, in the header.  (Stricter than it must be: the solver holds no fma at
     # all today; a later fma there that is no pivot may narrow this to fps_setup's region)
@@ -32,13 +35,13 @@ def test_solver_takes_its_pivots_from_the_header_and_its_layout_from_one_list():
     # no hand-summed block size beside the arena's list
     for old in ("n_mr", "n_pt", "total +"):
         assert old not in src, old
-    assert src.count("hipMalloc(&d.mem") == 1 and src.count("hipMemset(d.mem") == 1
+    assert cpp.count("hipMalloc(&d.mem") == 1 and cpp.count("hipMemset(d.mem") == 1
     # host-only: the header includes no HIP header (nor anything of the project's that does)
     inc = re.findall(r'#include\s*[<"]([^>"]+)[>"]', hdr)
     assert inc and not any("hip" in i or i.startswith("ns_") or "roc" in i for i in inc), inc
     # the direct solve's device pointers: one member of ns_solver
-    body = src.split("struct ns_solver {", 1)[1].split("\nnamespace {", 1)[0]
-    assert body.count("} fpd;") == 1
+    body = sh.split("struct ns_solver {", 1)[1].split("\n};\n", 1)[0]   # (the struct's own closing brace)
+    assert "} lo;" in body and body.count("} fpd;") == 1
     for old in ("fps_mem", "fps_tw", "fps_tw8", "fps_wk", "fps_ragg", "fps_gath", "fps_n", "s->fps_og", "s->og_b", "s->og_x1",
                 "s->m0[ebga]", "s->dF", "s->dG", "s->dense_mem"):
         assert not re.search(old + r"\b", src), old

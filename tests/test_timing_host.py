@@ -20,8 +20,9 @@ def test_recorder_host_program_under_sanitizers(tmp_path):
 
 
 def test_solver_has_one_timing_member_and_no_event_pool_of_its_own():
-    src = open(os.path.join(CSRC, "ns_solver.cpp")).read()
+    hdr = open(os.path.join(CSRC, "ns_solver.h")).read()
+    src = hdr + "".join(open(os.path.join(CSRC, f)).read() for f in ("ns_solver.cpp", "ns_observe.cpp"))
     for old in ("hipEventCreate(", "evtag", "hev", "hcomp", "kev["):
         assert old not in src, old
-    body = src.split("struct ns_solver {", 1)[1].split("\nnamespace {", 1)[0]
-    assert body.count("Timing ") == 1
+    body = hdr.split("struct ns_solver {", 1)[1].split("\n};\n", 1)[0]   # (the struct's own closing brace)
+    assert "} lo;" in body and body.count("Timing ") == 1

@@ -1,6 +1,7 @@
 // Host test of the kernel-timing recorder (navierstokessolver_amd/csrc/ns_timing.h) against a stub of the event
 // calls: a virtual clock instead of a GPU.  tests/test_timing_host.py compiles and runs it under the sanitizers.
 #include <cstdio>
+#include <cstring>
 #include <vector>
 
 #include "ns_timing.h"
@@ -44,6 +45,46 @@ static int timed_launch(T& tm, nsg::TKind kind, double ms, int weight = 1, bool 
     return iv.close();
 }
 
+// S's own kind lands in S and in no other struct; a drain into ns_stats releases its interval without counting it
+template <class S>
+static void observer(T& tm, nsg::TKind kind, double lat) {
+    CHECK(nsg::towned<S>() == nsg::tbit(kind) && nsg::trows<S>().size() == 1);
+    S own{};
+    ns_stats st, zero;
+    std::memset(&st, 0, sizeof st);
+    std::memset(&zero, 0, sizeof zero);
+    CHECK(timed_launch(tm, kind, 2.0, 3) == 0);
+    CHECK(tm.drain(~nsg::tbit(kind), &own) == 0 && own.n_kernels == 0);   // (not in the mask: kept)
+    CHECK(tm.drain(~0u, &own) == 0 && own.n_kernels == 3 && own.t_kernel_ms == 2.0 + lat);
+    CHECK(tm.drain(~0u, &own) == 0 && own.n_kernels == 3);                // (released)
+    own = S{};
+    CHECK(timed_launch(tm, kind, 2.0) == 0 && timed_launch(tm, nsg::T_K1, 1.0) == 0);
+    CHECK(tm.drain(~0u, &st) == 0 && st.n_rhs_kernels == 1 && st.t_rhs_kernel_ms == 1.0 + lat);
+    st.n_rhs_kernels = 0;
+    st.t_rhs_kernel_ms = 0.0;
+    CHECK(std::memcmp(&st, &zero, sizeof st) == 0);                       // (no line of ns_stats took it)
+    CHECK(tm.drain(~0u, &own) == 0 && own.n_kernels == 0 && own.t_kernel_ms == 0.0);
+    // ... and another struct's kinds leave S alone
+    CHECK(timed_launch(tm, nsg::T_HELM, 1.0) == 0 && timed_launch(tm, nsg::T_SCALAR_RHS, 1.0) == 0);
+    CHECK(tm.drain(~0u, &own) == 0 && own.n_kernels == 0 && own.t_kernel_ms == 0.0);
+}
+
+static void observers(T& tm, double lat) {
+    observer<ns_derived_stats>(tm, nsg::T_DERIVED, lat);
+    observer<ns_tracer_stats>(tm, nsg::T_TRACER, lat);
+    observer<ns_avg_stats>(tm, nsg::T_AVG, lat);
+    observer<ns_load_stats>(tm, nsg::T_LOADS, lat);
+    // every kind but T_RAW has exactly one owner (the header's static_assert, spelled out kind by kind)
+    for (int k = 0; k < nsg::T_NKIND; k++) {
+        const unsigned b = 1u << k;
+        const int owners = !!(nsg::towned<ns_stats>() & b) + !!(nsg::towned<ns_scalar_stats>() & b) +
+                           !!(nsg::towned<ns_derived_stats>() & b) + !!(nsg::towned<ns_tracer_stats>() & b) +
+                           !!(nsg::towned<ns_avg_stats>() & b) + !!(nsg::towned<ns_load_stats>() & b);
+        CHECK(owners == (k == nsg::T_RAW ? 0 : 1));
+    }
+    CHECK(nsg::trows<ns_stats>().size() == 11 && nsg::trows<ns_scalar_stats>().size() == 1);
+}
+
 static void run(bool stamped) {
     T tm;
     tm.stamped = stamped;
@@ -70,18 +111,19 @@ static void run(bool stamped) {
     CHECK(tm.drain(nsg::tbit(nsg::T_K5), &st) == 0 && st.n_k5_kernels == 1 && st.t_k5_kernel_ms == 7.0 + lat);
     // events are reused across steps: six intervals were the most alive at once
     CHECK(tm.events() == 12);
-    // the direct solve's phases share one count; the scalar's line goes to its own stats; null stats drop figures
+    // the direct solve's phases share one count; the scalar's line goes to its own stats; drop() counts nothing
     CHECK(timed_launch(tm, nsg::T_FPS_DCT, 1.0) == 0 && timed_launch(tm, nsg::T_FPS_TRI, 2.0, 1, true) == 0);
     CHECK(timed_launch(tm, nsg::T_FPS_IDCT, 3.0) == 0 && timed_launch(tm, nsg::T_SCALAR_RHS, 4.0) == 0);
     ns_scalar_stats ss{};
     st = ns_stats{};
-    CHECK(tm.drain(nsg::T_FPS | nsg::tbit(nsg::T_SCALAR_RHS), &st, &ss) == 0);
+    CHECK(tm.drain(nsg::T_FPS, &st) == 0 && tm.drain(nsg::tbit(nsg::T_SCALAR_RHS), &ss) == 0);
     CHECK(st.n_fps_solves == 1 && st.t_fps_dct_ms == 1.0 + lat && st.t_fps_idct_ms == 3.0 + lat);
     CHECK(st.t_fps_tri_ms == 3.0);   // (markers asked for: the latency counts in either mode)
     CHECK(ss.n_rhs_kernels == 1 && ss.t_rhs_kernel_ms == 4.0 + lat);
-    CHECK(timed_launch(tm, nsg::T_BAND, 1.0) == 0 && tm.drain(~0u, nullptr) == 0);
+    CHECK(timed_launch(tm, nsg::T_BAND, 1.0) == 0 && tm.drop(~0u) == 0);
     st = ns_stats{};
     CHECK(tm.drain(~0u, &st) == 0 && st.n_band_kernels == 0);
+    observers(tm, lat);
     {   // the empty interval: no launch took the stamp -- counted, (next to) no time, and the stamp is gone
         T::Scope iv;
         CHECK(tm.open(iv, nsg::T_BAND) == 0 && iv.close() == 0 && Stub::arm_a < 0);
